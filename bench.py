@@ -629,6 +629,50 @@ def slim(e):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000      # --dump-outputs: everything written, headers included
+DUMP_SAMPLE_SEED = 20240601            # the variants kept when a step's output is larger than that
+
+
+def output_arrays(out, fl, lmm, q):
+    """The timed path's results for one step as its caller receives them: (name, (V,) or (V, q) float64 host array) pairs.
+    LMM (sh_lmm_batch_dev): prep, pvalue, beta, bse, frac_h2; fixed effects (sh_glm_batch_dev): prep, pvalue, kbeta, bse, intercept,
+    betas; both: flags (uint32 notes and flags, exact in float64)."""
+    o = out.cpu().numpy()
+    names = ("prep", "pvalue", "beta", "bse", "frac_h2") if lmm else ("prep", "pvalue", "kbeta", "bse", "intercept")
+    arrs = [(n, np.ascontiguousarray(o[i], dtype=np.float64)) for i, n in enumerate(names)]
+    if not lmm:
+        arrs.append(("betas", np.ascontiguousarray(o[5:5 + q].T, dtype=np.float64)))
+    arrs.append(("flags", fl.cpu().numpy().view(np.uint32).astype(np.float64)))
+    return arrs
+
+
+def dump_outputs(d, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write every array as d/<name>.npy, and d/variant_index.npy: the variants (rows of every array) written.  Written are the variants
+    with a finite value in every array -- those the caller reports statistics for; the rest (AF- or pre-filtered: prep NaN, bse inf; a
+    fixed-effects fit without an answer: NaN) are left out and counted.  When all of them would exceed max_bytes, a fixed sample of them
+    (seeded, sorted) is written instead: the same rows on every run of the same arguments.  Returns what was written, for the result line."""
+    V = arrays[0][1].shape[0]
+    fin = np.ones(V, dtype=bool)
+    for _, a in arrays:
+        fin &= np.isfinite(a).reshape(V, -1).all(axis=1)
+    cand = np.flatnonzero(fin)
+    per_variant = 8 * (1 + sum(int(np.prod(a.shape[1:])) for _, a in arrays))       # the index array included
+    room = max_bytes - 256 * (len(arrays) + 1)                                          # .npy headers
+    n = min(cand.size, room // per_variant)
+    if n < cand.size:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(cand, n, replace=False))
+    else:
+        idx = cand
+    os.makedirs(d, exist_ok=True)
+    names = [name for name, _ in arrays] + ["variant_index"]
+    np.save(os.path.join(d, "variant_index.npy"), idx.astype(np.float64))
+    for name, a in arrays:
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a[idx]))
+    nbytes = sum(os.path.getsize(os.path.join(d, f + ".npy")) for f in names)
+    return {"dir": os.path.abspath(d), "arrays": names, "variants": int(n), "of_variants": int(V), "not_finite_left_out": int(V - cand.size),
+            "bytes": int(nbytes)}
+
+
 def fixed_effects_summary(extra):
     """BASELINE's metric is "LMM and fixed-effects at N = 5000": the fixed-effects half as top-level numbers of the line."""
     def one(e):
@@ -688,7 +732,13 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle re-check of the timed output")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for the one-GPU test)")
     ap.add_argument("--one-device", action="store_true", help="test only: every rank uses cuda:0 (exercises the N > 1 code path on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's results of the last timed step as DIR/<name>.npy (float64, the variants with "
+                         "finite results, at most 64 MB: a fixed sample of them when the step's output is larger; DIR/variant_index.npy "
+                         "says which)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -803,6 +853,7 @@ def main():
 
     if rank == 0:
         last = bits[(args.warmup + args.steps - 1) % ndist]
+        dumped = dump_outputs(args.dump_outputs, output_arrays(out, fl, lmm, q)) if args.dump_outputs else None
         total = float(Vs) * args.steps * world
         value = total / dt
         # LMM: the HIP-event time of the contraction kernel per launch.  Fixed effects on the lanes: the batches of different lanes overlap on
@@ -813,6 +864,8 @@ def main():
                "data": "synthetic", "world": world, "rccl_ranks_seen": ranks_seen, "collective_backend": args.backend if world > 1 else None,
                "per_rank_value": per_rank, "finite_fraction": min(fin_all),
                "distinct_rows_per_gpu": int(ndist) * int(Vs)}
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if lmm:
             info = eng.lmm_info()                         # after the timed launches: the MACs the contraction kernel actually issued per variant
             int8_ops = 2.0 * info["int8_macs_per_variant"] * Vs

@@ -103,12 +103,17 @@ def test_fixed_effects_golden(path):
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(G, "glm_*.npz"))))
 def test_forced_firth_golden(path):
-    """BASELINE config C4: every variant through fit_firth (model.py:414)."""
+    """BASELINE config C4: every variant through fit_firth (model.py:414).  With the fixture's prefilter active (pret < 1), the rows it
+    removes (model.py:266) are not fitted: they keep the reference's prep and flags and no statistic; every other row is fitted by Firth."""
     d = np.load(path)
-    if float(d["pret"]) < 1:
-        pytest.skip("prefilter active in this fixture")
     r = _run(d, force_firth=True)
-    ok = d["firth_ok"] == 1
+    pf = d["prefilter"] == 1
+    assert (((r["flags"] >> 16) & 1) == d["prefilter"]).all()
+    if pf.any():
+        close(r["prep"][pf], d["main"][pf, 0], atol=1e-300, what="prep of prefiltered rows")
+        for f in ("pvalue", "kbeta", "bse", "intercept"):
+            assert np.isnan(r[f][pf]).all(), f
+    ok = (d["firth_ok"] == 1) & ~pf
     if "bincov" in path:
         ok[[8, 9]] = False
     fm = d["firth_main"]

@@ -674,18 +674,18 @@ def test_lmm_state_shared_between_contexts(engine_mod):
 
 
 def test_sharded_engine_across_real_devices(engine_mod):
-    """ShardedEngine over every visible GPU (skipped on a one-GPU box): same numbers as one context, input order kept."""
+    """ShardedEngine over every visible GPU (on a one-GPU box: two contexts of it), per-run state shared from the first context:
+    same numbers as one context, input order kept."""
     Engine, pack = engine_mod
     import torch
     from pyseer_amd.parallel import ShardedEngine
     nd = torch.cuda.device_count()
-    if nd < 2:
-        pytest.skip("one GPU visible")
+    devices = list(range(nd)) if nd > 1 else [0, 0]
     d = np.load(os.path.join(G, "lmm_N300_D3.npz"))
     bits = pack(np.tile(d["Kv"], (40, 1))[:2001])
     e = Engine(300); e.lmm_setup(d["U"], d["S"], d["y"], d["covar"], float(d["h2"]))
     want = e.lmm_batch(bits); e.close()
-    s = ShardedEngine(300, list(range(nd)))
+    s = ShardedEngine(300, devices)
     s.lmm_setup(d["U"], d["S"], d["y"], d["covar"], float(d["h2"]))
     got = s.lmm_batch(bits); s.close()
     for k in want:
