@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- k-mer tests/second of the per-variant association hot path on MI355X (BASELINE.json configs C2 / C3 / C4).
 
-    python bench.py --gpus 1 --steps K --warmup W [--config C3|C2|C2N5000|C4]
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--config C3|C2|C2N5000|C4] [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic packed k-mer presence rows that already live in HBM:
   C3 (default)  LMM, N = 5000, D = 1: sh_lmm_batch_dev = repack -> linear terms -> int8-MFMA quadratic form -> finalise
@@ -10,8 +10,11 @@ A "step" is one pass of the hot path over one batch of synthetic packed k-mer pr
   C2N5000       the same at N = 5000 (the "fixed-effects at N = 5000" half of BASELINE's metric)
   C4            N = 5000, 10 covariates, every variant through Firth (force_firth)
 The k-mer stream shards across ranks with no collective on the data path (weak scaling: every rank tests its own
---variants-per-step rows per step).  One JSON line is printed by rank 0; it carries `roofline`, `cpu_baseline` (N = 1) and
-`parity_checked` = number of variants of the TIMED output that were re-checked against the CPU oracle after the timed region.
+--variants-per-step rows per step).  One JSON line is printed by rank 0; it carries the value and `roofline` of the timed steps.
+A plain run does nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full the
+line also carries `parity_checked` = number of variants of the TIMED output that were re-checked against the CPU oracle after the
+timed region, `cpu_baseline` (N = 1) and the secondary measurements (N = 1: `extra` / `fixed_effects_n5000` of C3, `synchronous` of
+the fixed-effects configurations); --no-parity / --no-cpu-baseline / --no-extra leave parts of that out.
 """
 import argparse
 import json
@@ -414,7 +417,7 @@ def glm_lanes_line(eng, cfg, bits, q, Vs, rb, steps=15, warmup=None, check=None)
 
 def fixed_effects_line(cfg, dev, local, steps=5, warmup=1, Vs=None, cpu=True, parity=True, env=None):
     """One fixed-effects configuration measured the way the main line is (HIP events on the launch stream, inputs resident, oracle re-check
-    of the timed output, CPU baseline): the `extra` entries of the default (C3) line, so that the driver's run of `bench.py --gpus 1`
+    of the timed output, CPU baseline): the `extra` entries of the C3 line, so that `bench.py --gpus 1 --full`
     carries both halves of BASELINE's metric (LMM and fixed effects at N = 5000).  env: switches read by sh_glm_setup (e.g. the literal
     Firth step-halving rule)."""
     import torch
@@ -727,9 +730,13 @@ def main():
     ap.add_argument("--config", default="C3", choices=["C3", "C2", "C2N5000", "C4"])
     ap.add_argument("--variants-per-step", type=int, default=0, help="default: 2^20 (C3, C2), 2^18 (C2N5000, C4)")
     ap.add_argument("--limbs", type=int, default=0, help="int8 limbs of the LMM contraction (0 = the library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary fixed-effects measurements of the C3 line")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle re-check of the timed output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also re-check the timed output against the CPU oracle, time the CPU baseline and run the "
+                         "secondary measurements (C3: the fixed-effects configurations, other limb counts, host pointers; fixed effects: "
+                         "the synchronous call); a plain run does only what the headline value needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle re-check of the timed output")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for the one-GPU test)")
     ap.add_argument("--one-device", action="store_true", help="test only: every rank uses cuda:0 (exercises the N > 1 code path on a 1-GPU box)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -763,6 +770,10 @@ def main():
     ranks_seen = par.ranks_connected(cdev)
     if world > 1:
         assert ranks_seen == world == dist.get_world_size(), (ranks_seen, world)
+    # what runs after the timed steps besides the headline (--full only; the CPU baseline and secondary lines on one GPU only)
+    parity = args.full and not args.no_parity
+    extra = args.full and world == 1 and not args.no_extra
+    cpu = args.full and world == 1 and not args.no_cpu_baseline
 
     from pyseer_amd.engine import Engine, row_bytes_for
     cfg = args.config
@@ -888,29 +899,28 @@ def main():
                 "error_bound": {k: info[k] for k in ("quant_err_norm", "quant_err_norm_power_iteration", "quant_err_norm_squarings", "bound_rel_typical",
                                                      "refined_last_batch") if k in info},
             })
-            if not args.no_parity:
+            if parity:
                 n, devs = parity_lmm(U, S, y, C, h2, last, out, N)
                 res["parity_checked"] = n; res["parity_max_rel_dev"] = devs
                 assert max(devs.values()) < 1e-6, "timed output deviates from the oracle: %s" % devs
-            if world == 1 and not args.no_extra:
+            if extra:
                 # the rest of BASELINE's metric ("LMM and fixed-effects at N = 5000") on the same line: each entry is measured like a main line
                 # (event-timed kernels, counted roofline, oracle re-check, CPU baseline).  C4_literal: the reference's literal step-halving rule.
-                cpu = not args.no_cpu_baseline
                 nb3 = min(3, len(bits))
                 res["extra"] = {
-                    "C2N5000": fixed_effects_line("C2N5000", dev, local, cpu=cpu, parity=not args.no_parity),
-                    "C4": fixed_effects_line("C4", dev, local, cpu=cpu, parity=not args.no_parity),
-                    "C4_literal": fixed_effects_line("C4", dev, local, cpu=False, parity=not args.no_parity, env={"SEERHIP_ROUTE": "firth_literal=1"}),
-                    "C2": fixed_effects_line("C2", dev, local, steps=3, cpu=cpu, parity=not args.no_parity),
+                    "C2N5000": fixed_effects_line("C2N5000", dev, local, cpu=cpu, parity=parity),
+                    "C4": fixed_effects_line("C4", dev, local, cpu=cpu, parity=parity),
+                    "C4_literal": fixed_effects_line("C4", dev, local, cpu=False, parity=parity, env={"SEERHIP_ROUTE": "firth_literal=1"}),
+                    "C2": fixed_effects_line("C2", dev, local, steps=3, cpu=cpu, parity=parity),
                     # a caller that holds ONE batch at a time (no lanes to fill): what a large call buys -- the `synchronous` entry of these two is
                     # one sh_glm_batch_dev of 2^20 rows per step on one stream, beside the same rows through the lanes
-                    "C2N5000_calls_of_2e20_rows": fixed_effects_line("C2N5000", dev, local, steps=3, Vs=1 << 20, cpu=False, parity=not args.no_parity),
-                    "C4_calls_of_2e20_rows": fixed_effects_line("C4", dev, local, steps=3, Vs=1 << 20, cpu=False, parity=not args.no_parity),
+                    "C2N5000_calls_of_2e20_rows": fixed_effects_line("C2N5000", dev, local, steps=3, Vs=1 << 20, cpu=False, parity=parity),
+                    "C4_calls_of_2e20_rows": fixed_effects_line("C4", dev, local, steps=3, Vs=1 << 20, cpu=False, parity=parity),
                     "C3_five_limbs": lmm_variant_line(U, S, y, C, h2, dev, local, bits[:nb3], 3, limbs=5),
                     "C3_all_refined_56bit": lmm_variant_line(U, S, y, C, h2, dev, local, bits[:nb3], 3, limbs=0, tol=1e-300),
                     "C3_host_pointers_pcie_inclusive": lmm_host_pointer_line(U, S, y, C, h2, dev, local, bits[0], 4),
                 }
-            if world == 1 and not args.no_cpu_baseline:
+            if cpu:
                 res["cpu_baseline"] = cpu_baseline_lmm(U, S, y, C, h2, N)
         else:
             force = cfg == "C4"
@@ -920,10 +930,10 @@ def main():
             res["config"]["workload"] += ", one engine context, batches through its %d lanes" % lanes
             res["roofline"]["batch_span_ms"] = kms / max(klaunch, 1)
             res["roofline"]["kernel_ms_is"] = "timed region / steps (the batches of different lanes overlap; batch_span_ms = one batch's own HIP-event span on its lane's stream)"
-            if not args.no_parity:
+            if parity:
                 n, devs = parity_glm(y, W, nl, nf, force, last, out, fl, N)
                 res["parity_checked"] = n; res["parity_max_rel_dev"] = devs
-            if world == 1 and not args.no_extra:
+            if extra:
                 # the same context, one synchronous sh_glm_batch_dev per step on one stream (rounds 1-4's measurement), and its rows for the
                 # last timed batch: the lanes' must be the same bytes
                 try:
@@ -944,7 +954,7 @@ def main():
                     del o1, f1
                 except Exception as e:
                     res["synchronous"] = {"error": repr(e)}
-            if world == 1 and not args.no_cpu_baseline:
+            if cpu:
                 res["cpu_baseline"] = cpu_baseline_glm(y, W, nl, nf, N, force)
         emit(res)
     if world > 1:

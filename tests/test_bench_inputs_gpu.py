@@ -234,7 +234,7 @@ def test_bench_ranks_on_one_gpu(tmp_path, world):
     vs = 65536 if world == 2 else 32768
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29517 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--variants-per-step", str(vs), "--backend", "gloo", "--one-device"]
+           "--variants-per-step", str(vs), "--backend", "gloo", "--one-device", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -274,6 +274,34 @@ def test_bench_dump_outputs_repeat(tmp_path):
         assert (got["flags.npy"].astype(np.int64) & ((1 << 16) | 1 | 64) == 0).all()   # no AF-/pre-filtered row, no firth-fail
         runs.append(got)
     assert all(np.array_equal(runs[0][f], runs[1][f], equal_nan=True) for f in runs[0])
+
+
+def test_bench_full_adds_checks_after_the_plain_run(tmp_path):
+    """A plain bench.py run carries the timed steps' numbers only; --full adds the oracle re-check and the synchronous call after the
+    timed steps (the CPU baseline left out here: it takes seconds of its own) and leaves the timed steps' results as they were."""
+    import json
+    import subprocess
+    env = dict(os.environ); env["PYTHONPATH"] = ROOT
+    lines, dumped = [], []
+    for k, more in enumerate(([], ["--full", "--no-cpu-baseline"])):
+        d = tmp_path / str(k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C2", "--steps", "2", "--warmup", "1",
+               "--variants-per-step", "65536", "--dump-outputs", str(d)] + more
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        dumped.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    plain, full = lines
+    for line in lines:
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["finite_fraction"] == 1.0
+        assert {"metric", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"} <= set(line)
+    assert not {"parity_checked", "cpu_baseline", "synchronous", "identical_to_synchronous_call", "extra"} & set(plain)
+    # (how close the bench's own rows come to the oracle: test_c2_logistic_bench_inputs_vs_oracle)
+    assert full["parity_checked"] > 0 and {"pvalue", "kbeta", "bse", "intercept", "notes_equal"} <= set(full["parity_max_rel_dev"])
+    assert full["identical_to_synchronous_call"] and full["synchronous"]["value"] > 0
+    assert "cpu_baseline" not in full
+    assert plain["metric"] == full["metric"] and plain["dtype"] == full["dtype"]
+    assert list(dumped[0]) == list(dumped[1]) and all(np.array_equal(dumped[0][f], dumped[1][f]) for f in dumped[0])
 
 
 def test_bench_one_rank_under_torchrun_equals_the_plain_launch():

@@ -13,7 +13,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 CFGS=${CFGS:-"C3 C2 C2N5000 C4"}
 for c in $CFGS; do
-  python $R/bench.py --config $c --steps 10 --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err
+  python $R/bench.py --config $c --steps 10 --warmup 2 --full > $O/bench_$c.json 2> $O/bench_$c.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$c -- python $R/bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-extra --no-parity > $O/stats_$c.json 2> $O/stats_$c.err
 done
 pmc() {  # cfg group counters...

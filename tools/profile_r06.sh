@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-6 profiling recipe (run on the GPU box through gpurun).  For every bench configuration:
-#   1. the bench line itself (C3 = the default invocation, i.e. what the driver runs, `extra` included)   -> bench_<cfg>.json
+#   1. the full bench line (bench.py --full: C3 with `extra`, oracle re-check, CPU baseline)                -> bench_<cfg>.json
 #   2. rocprofv3 --kernel-trace --stats of the same command (without the CPU legs)                          -> stats_<cfg>/
 #   3. PMC passes in their own runs, one counter group per run (never combined with the trace domains gpurun refuses): FETCH_SIZE,
 #      WRITE_SIZE, GRBM_GUI_ACTIVE, SQ issue / wait cycles + SQ_INSTS_VALU, fp64 / fp32 / f16 instruction counts (fixed effects), L2 hits
@@ -10,8 +10,8 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r06; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 CFGS=${CFGS:-"C3 C2N5000 C4 C2"}
 for c in $CFGS; do
-  if [ "$c" = "C3" ]; then python $R/bench.py --steps 10 --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err
-  else python $R/bench.py --config $c --steps 12 --warmup 6 > $O/bench_$c.json 2> $O/bench_$c.err; fi
+  if [ "$c" = "C3" ]; then python $R/bench.py --steps 10 --warmup 2 --full > $O/bench_$c.json 2> $O/bench_$c.err
+  else python $R/bench.py --config $c --steps 12 --warmup 6 --full > $O/bench_$c.json 2> $O/bench_$c.err; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$c -- python $R/bench.py --config $c --steps 6 --warmup 3 --no-cpu-baseline --no-extra --no-parity > $O/stats_$c.json 2> $O/stats_$c.err
   # fixed effects: the same steps on ONE lane (no two batches on the device at once): per-kernel durations that are the kernels' own
   [ "$c" != "C3" ] && SEERHIP_ROUTE=lanes=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1_$c -- python $R/bench.py --config $c --steps 6 --warmup 3 --no-cpu-baseline --no-extra --no-parity > $O/stats1_$c.json 2> $O/stats1_$c.err
