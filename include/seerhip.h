@@ -333,6 +333,35 @@ int     sh_host_cpu_seconds(char *buf, int cap);
 /* the largest number of threads that were inside sh_format_rows / sh_format_records at the same time (reset != 0 clears it): tests */
 int     sh_format_concurrency_max(int reset);
 
+/* ---------------------------------------------------------------------------------------------
+ * Native VCF reader (csrc/vcf_reader.cpp + csrc/vcf_kernels.hip; replaces the 'vcf' branch of pyseer/input.py:301 read_variant and
+ * read_vcf_var, input.py:455-503, for the GPU feed).  VCF text -- plain, gzip or BGZF; no index file is read -- is decoded, framed and
+ * its nine fixed columns parsed on the host; the sample columns go to the device as they stand and k_vcf_gt_pack reduces every sample's
+ * GT to present / missing / absent.  Bound to a context because it uses its device and stream; ctx == NULL selects the host restatement of
+ * the kernel (measurements, and checks where there is no device) -- the command line never passes NULL.
+ *   sh_vcf_next: up to max_records records -> per record the skip reason (0 kept, 1 more than one ALT, 2 FILTER neither empty nor PASS;
+ *   skipped records have rows of zeros), POS, len(REF), the contig's id (sh_vcf_contig), and two packed rows over sample_names in the
+ *   engine's layout (LSB first, row_bytes as sh_lmm_batch): `present` and `missing` (a sample is never in both) with their popcounts.
+ *   Returns the number of records, 0 at the end of the file, -1 on error (sh_last_error).
+ *   sh_vcf_names: the names CHROM_POS_REF[_ALT] of the LAST sh_vcf_next as one blob + offsets (layout of sh_reader_next), owned by the
+ *   reader and valid until its next call; returns the blob's length.
+ *   sh_burden_fold: burden variant v = records csr_idx[csr_off[v] .. csr_off[v+1]) of a batch of rows, in application order: present =
+ *   OR of their present rows, missing = the LAST record's missing row where not present (input.py:383-407); host pointers.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sh_vcf sh_vcf;
+sh_vcf     *sh_vcf_open(sh_ctx *ctx, const char *path, const char *const *sample_names, int n_samples);
+void        sh_vcf_close(sh_vcf *r);
+int64_t     sh_vcf_next(sh_vcf *r, int64_t max_records, int32_t *skip, int64_t *pos, int32_t *ref_len, int32_t *contig, uint8_t *present, uint8_t *missing,
+                        int64_t row_bytes, int32_t *n_present, int32_t *n_missing);
+int64_t     sh_vcf_names(sh_vcf *r, const char **blob, const int64_t **name_off);
+/* mode: 0 plain, 1 gzip, 2 BGZF; the sample columns of the header; contigs met so far */
+int         sh_vcf_info(sh_vcf *r, int *mode, int *n_cols, int *n_contigs);
+const char *sh_vcf_contig(sh_vcf *r, int id);
+/* bytes of sample columns handed to the tokeniser, records delivered, kernel launches so far */
+int         sh_vcf_stats(sh_vcf *r, int64_t *sample_bytes, int64_t *records, int64_t *launches);
+int         sh_burden_fold(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t n_records, const int64_t *csr_off,
+                           const int32_t *csr_idx, int64_t n_variants, uint8_t *out_present, uint8_t *out_missing, int32_t *n_present, int32_t *n_missing);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """`python -m pyseer_amd` -- pyseer's command line for the per-variant association tests, driving the HIP engine.
 
-Mirrors pyseer/__main__.py for the options that reach the hot path: k-mer / Rtab input, fixed effects (SEER) with MDS of
+Mirrors pyseer/__main__.py for the options that reach the hot path: k-mer / Rtab / VCF input (--vcf, with --burden regions), fixed effects (SEER) with MDS of
 a distance matrix or --no-distances, --lmm with a similarity matrix or --load-lmm cache, covariates, continuous
 phenotypes, the AF / missing / p-value filters, --print-samples / --print-filtered / --output-patterns, and the four
 end-of-run counters.  Variants are parsed in blocks of --block_size, packed, and tested block-wise on the GPU; rows are
@@ -9,7 +9,8 @@ tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 
 --lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 16).
 
-Not supported (out of scope): --vcf/--burden (pysam), --wg (enet/rf).
+VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
+reader (--python-reader).  Not supported (out of scope): --wg (enet/rf), BCF, and --gpus / the packed cache with a VCF.
 """
 import argparse
 import os
@@ -86,6 +87,7 @@ from . import __version__
 from .classes import Seer, LMM, FLAG_FILTER, FLAG_PREFILTER, notes_from_flags
 from .input import (check_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
                     iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_native_multi, iter_packed_blocks_cached,
+                    iter_packed_blocks_vcf_native, load_burden,
                     PackedCacheWriter, packed_cache_complete)
 from .lmm import initialise_lmm, mask_like_fit_lmm
 from .model import fit_null, covariate_block
@@ -102,9 +104,10 @@ def get_options(argv=None):
     vg = va.add_mutually_exclusive_group(required=True)
     vg.add_argument('--kmers', default=None, nargs='+',
                     help='Kmers file; several files are tested as one stream in the order given and read concurrently (one gzip stream inflates serially)')
-    vg.add_argument('--vcf', default=None, help='VCF file (not supported by this build)')
+    vg.add_argument('--vcf', default=None, help='VCF file. Will filter any non \'PASS\' sites')
     vg.add_argument('--pres', default=None, help='Presence/absence .Rtab matrix as produced by roary and piggy')
-    va.add_argument('--burden', help='(not supported by this build)')
+    va.add_argument('--burden', help='VCF regions to group variants by for burden testing (requires --vcf). '
+                    'The regions are assigned in one pass over the file: no index is needed or read')
     di = parser.add_argument_group('Distances')
     dg = di.add_mutually_exclusive_group()
     dg.add_argument('--distances', help='Strains distance square matrix (fixed or lineage effects)')
@@ -156,7 +159,7 @@ def get_options(argv=None):
     ot.add_argument('--no-dedup', action='store_true', default=False,
                     help='Test every variant separately [Default: each distinct presence pattern of a block is tested once]')
     ot.add_argument('--python-reader', action='store_true', default=False,
-                    help='Parse k-mer files with the Python reader instead of the native C++ one')
+                    help='Parse k-mer and VCF files with the Python reader instead of the native one')
     ot.add_argument('--python-sink', action='store_true', default=False,
                     help='Format every output row in Python (one result tuple per variant) instead of the native block sink')
     ot.add_argument('--serial-sink', action='store_true', default=False,
@@ -188,8 +191,10 @@ def main(argv=None):
             # HIP runtime underneath it, and importing torch now would break the device for both)
             sys.stderr.write("pyseer_amd: kinship decomposition on the CPU (numpy) for this run\n")
             options.cpu_eigh = True
-    if options.vcf or options.burden:
-        _die('VCF / burden input needs pysam and is not supported by pyseer_amd\n')
+    if options.burden and not options.vcf:
+        _die('Burden test can only be performed with VCF input\n')
+    if options.vcf and (options.gpus is not None or options.save_packed or options.load_packed or options.packed_cache or options.packed_part):
+        _die('--gpus and the packed cache (--save-packed / --load-packed / --packed-cache / --packed-part) are not available with --vcf\n')
     if options.wg:
         _die('Whole-genome models (--wg) are out of scope for pyseer_amd\n')
     if options.max_dimensions < 1:
@@ -363,8 +368,13 @@ def main(argv=None):
         _die('--save-packed and --load-packed name the same file\n')
     if len(kmer_files) > 1 and (options.python_reader or options.load_packed or options.save_packed or options.packed_cache):
         _die('Several --kmers files need the native reader and cannot be combined with a packed cache\n')
-    var_type, var_file = ("kmers", kmer_files[0]) if kmer_files else ("Rtab", options.pres)
+    var_type, var_file = ("kmers", kmer_files[0]) if kmer_files else (("vcf", options.vcf) if options.vcf else ("Rtab", options.pres))
     native = (var_type == "kmers") and not options.python_reader
+    native_vcf = (var_type == "vcf") and not options.python_reader
+    burden_regions = None
+    if options.burden:
+        import collections as _collections
+        burden_regions = _collections.deque([])
     if native or options.load_packed:
         # blocks of the native reader / the packed cache hand every parsed row to the engine (input.py _block_from_raw): the AF window is applied
         # on the device as well, so filtered rows are neither copied out on the host nor contracted on the GPU
@@ -376,8 +386,11 @@ def main(argv=None):
                 if fh.read(2) != b"\x1f\x8b":
                     sys.stderr.write("Not a gzipped file (%s): use --uncompressed for plain-text k-mers\n" % vf)
                     sys.exit(1)
-    if not native:
-        infile, sample_order = open_variant_file(var_type, var_file, None, None, options.uncompressed)
+    if native_vcf:
+        if options.burden:
+            load_burden(options.burden, burden_regions)
+    elif not native:
+        infile, sample_order = open_variant_file(var_type, var_file, options.burden, burden_regions, options.uncompressed)
     patterns = open(options.output_patterns, 'wb') if options.output_patterns else None
 
     header = ['variant', 'af', 'filter-pvalue', 'lrt-pvalue', 'beta', 'beta-std-err']
@@ -459,9 +472,14 @@ def main(argv=None):
         blocks = iter_packed_blocks_native(p, var_file, options.min_af, options.max_af, job_block,
                                            want_patterns=bool(options.output_patterns), want_samples=options.print_samples,
                                            save_to=cache_out, raw=job_path)
+    elif native_vcf:
+        # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
+        blocks = iter_packed_blocks_vcf_native(p, var_file, engs[0], options.min_af, options.max_af, options.max_missing, options.block_size,
+                                               burden_regions=(list(burden_regions) if options.burden else None))
     else:
         blocks = iter_packed_blocks(p, var_type, infile, all_strains, sample_order, options.min_af, options.max_af,
-                                    options.max_missing, options.uncompressed, options.block_size)
+                                    options.max_missing, options.uncompressed, options.block_size,
+                                    burden=bool(options.burden), burden_regions=burden_regions)
     # ---- block sink (csrc/writer.cpp): results stay arrays from the engine to the TSV text; the per-variant tuple path below
     # is kept for --print-samples, for variants carrying missing calls, and as the cross-check (--python-sink)
     from .sink import RowFormatter, names_blob
@@ -610,7 +628,7 @@ def main(argv=None):
             ident = r is not None and isinstance(blk.row_of, np.ndarray) and nb == r["flags"].shape[0]
             j = None if ident else row_of[on]
             flags = np.zeros(nb, dtype=np.uint32)
-            flags[status == 1] = NOTE_AF | FLAG_PREFILTER
+            flags[(status == 1) | (status == 3)] = NOTE_AF | FLAG_PREFILTER
             keys = ("prep", "pvalue", "beta", "bse", "frac_h2") if options.lmm else ("prep", "pvalue", "kbeta", "bse", "intercept")
             cols = [np.asarray(blk.afs, dtype=np.float64)]
             for kname in keys:
@@ -659,7 +677,7 @@ def main(argv=None):
             tested += nb - npf
             if patterns is not None:
                 patterns.write(b''.join(blk.patterns[i] for i in order if not pf[i]))
-            show = np.ones(nb, dtype=bool) if options.print_filtered else (~pf & ~ft)
+            show = (status != 3) if options.print_filtered else (~pf & ~ft)      # (a skipped VCF record has no name: counted, never a row)
             sel = order[show[order]]
             printed += int(sel.shape[0])
             if sel.shape[0]:
@@ -710,6 +728,7 @@ def main(argv=None):
 
         def after_engine(blk, r):
             """Everything that follows a block's engine call: hand it to the sink (array-backed), or build the reference's row objects."""
+            nonlocal prefilter
             if not options.python_sink and not options.print_samples and 2 not in blk.status:
                 if overlap:
                     if sink_err:
@@ -726,6 +745,9 @@ def main(argv=None):
             rows = []
             for i, name in enumerate(blk.names):
                 st, af, ks, nks = blk.status[i], blk.afs[i], blk.kstrains[i], blk.nkstrains[i]
+                if st == 3:                                   # a skipped VCF record: loaded and pre-filtered (input.py:608, :693), never a row
+                    rows.append(None)
+                    continue
                 if st == 1:                                   # AF / missing filtered (model.py:255-260, lmm.py:160-167)
                     if options.lmm:
                         rows.append(LMM(name, None, af, nan, nan, nan, nan, nan, None, ks, nks, {'af-filter'}, True, False))
@@ -766,7 +788,7 @@ def main(argv=None):
             if options.lineage:
                 # fit_lineage_effect: fixed effects -> every variant that reached the fit (model.py:379-382; firth-fail and
                 # missing-data return earlier); LMM -> only variants that pass the LRT filter (lmm.py:209-213)
-                need = [i for i, x in enumerate(rows) if blk.status[i] == 0 and not x.prefilter and
+                need = [i for i, x in enumerate(rows) if x is not None and blk.status[i] == 0 and not x.prefilter and
                         ((not x.filter) if options.lmm else ('firth-fail' not in x.notes))]
                 if options.lmm and not options.lmm_lineage_per_variant:
                     # Reference behaviour (pyseer/lmm.py:209-213): inside fit_lmm's second loop `k` still holds the LAST variant
@@ -777,12 +799,14 @@ def main(argv=None):
                         from .packing import pack_variants
                         ml = int(eng.lineage_batch(pack_variants(np.asarray(kl).reshape(1, -1)))[0])
                     for i, x in enumerate(rows):
-                        if not x.prefilter and not x.filter:
+                        if x is not None and not x.prefilter and not x.filter:
                             rows[i] = x._replace(max_lineage=(None if ml < 0 else ml))
                 elif need:
                     ml = eng.lineage_batch(blk.bits[[blk.row_of[i] for i in need]])
                     for i, v in zip(need, ml):
                         rows[i] = rows[i]._replace(max_lineage=(None if v < 0 else int(v)))
+            prefilter += sum(1 for x in rows if x is None)
+            rows = [x for x in rows if x is not None]
             if options.lmm:                                   # fit_lmm's return order: filtered first, then tested
                 rows = [x for x in rows if x.prefilter] + [x for x in rows if not x.prefilter]
             for x in rows:

@@ -94,6 +94,17 @@ SIGNATURES = {
     "sh_host_pool_workers": (C.c_int, []),
     "sh_host_cpu_seconds": (C.c_int, [C.c_char_p, C.c_int]),
     "sh_format_concurrency_max": (C.c_int, [C.c_int]),
+    # the native VCF reader (csrc/vcf_reader.cpp, csrc/vcf_kernels.hip)
+    "sh_vcf_open": (C.c_void_p, [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
+    "sh_vcf_close": (None, [C.c_void_p]),
+    "sh_vcf_next": (C.c_int64, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_u8p, c_u8p,
+                                C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sh_vcf_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "sh_vcf_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sh_vcf_contig": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "sh_vcf_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sh_burden_fold": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, c_u8p, c_u8p,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -20,6 +20,8 @@
 
 // ---- kernel launchers (lmm_kernels.hip / glm_kernels.hip) -----------------------------------------------------
 #include "lmm_params.h"
+#include "vcf_kernels.h"
+#include "vcf_reader.h"
 extern "C" {
 hipError_t shk_sim_accumulate(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, double min_af, double max_af,
                               int af_on, uint64_t *keep, uint64_t *S, int NS, unsigned long long *Kacc);
@@ -1120,5 +1122,6 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "lanes_api.inc"
 #include "job_api.inc"
 #include "job_run.inc"
+#include "vcf_api.inc"
 
 }  // extern "C"

@@ -3,12 +3,15 @@
 The generators keep the reference's tuple layouts (iter_variants: the 16-tuple that is the argument list of
 fixed_effects_regression, input.py:608-620; load_var_block: (variants, variant_mat, eof), input.py:678-707) so existing
 callers keep working; `iter_packed_blocks` is the feed of the GPU driver: the same parsing, but presence goes straight
-into packed bit rows.  VCF input needs pysam (absent here) and is not supported.
+into packed bit rows.  VCF input (pyseer/input.py:250-266, 383-407, 455-503) is read as text -- plain, gzip or BGZF -- by `VcfFile`
+(the `--python-reader` path and the yardstick) or by the native reader whose sample columns are tokenised on the device (`NativeVcfReader`,
+csrc/vcf_reader.cpp + csrc/vcf_kernels.hip).  No tabix index is read: burden regions are assigned in one pass over the file.
 """
 import binascii
 import gzip
 import hashlib
 import os
+import re
 import sys
 
 import numpy as np
@@ -131,8 +134,174 @@ def load_lineage(infile, p):
     return mat, lineages
 
 
+def load_burden(infile, burden_regions):
+    """Append (name, [region, ...]) per line `NAME region[,region...]` of the regions file to burden_regions (input.py:250-266)."""
+    with open(infile, "r") as region_file:
+        for line in region_file:
+            name, regions = line.rstrip().split()
+            burden_regions.append((name, regions.split(',')))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# VCF as text (DESIGN.md, "VCF input"): what the reference takes from pysam's records is the contig, the position, the alleles, FILTER and
+# every sample's GT (input.py:455-503); all of it is in the tab-separated line.
+# ---------------------------------------------------------------------------------------------------------------
+VCF_KEPT, VCF_MULTI, VCF_FILTERED = 0, 1, 2          # skip reasons (include/seerhip.h sh_vcf_next)
+GT_ABSENT, GT_PRESENT, GT_MISSING = 0, 1, 2
+
+
+def gt_code(gt):
+    """The three-way code of one GT string: present as soon as one haplotype is a non-zero allele index (any digit 1-9: separators are
+    `/` and `|`, everything else in a well-formed GT is digits and `.`); otherwise absent if the LAST haplotype holds a 0, else missing."""
+    for c in gt:
+        if '1' <= c <= '9':
+            return GT_PRESENT
+    last = gt[max(gt.rfind('/'), gt.rfind('|')) + 1:]
+    return GT_ABSENT if '0' in last else GT_MISSING
+
+
+class VcfRecord(object):
+    __slots__ = ("contig", "pos", "ref", "alt", "skip", "name", "gt_index", "fields")
+
+    def __init__(self, line):
+        f = line.rstrip('\r\n').split('\t')
+        f += [''] * (9 - len(f))
+        self.contig, self.pos, self.ref, self.alt = f[0], int(f[1]), f[3], f[4]
+        flt = [x for x in f[6].split(';') if x not in ('', '.')]
+        self.skip = VCF_MULTI if ',' in self.alt else (VCF_FILTERED if (flt and 'PASS' not in flt) else VCF_KEPT)
+        self.name = "_".join([self.contig, f[1], self.ref] + ([] if self.alt in ('.', '') else [self.alt]))
+        fmt = f[8].split(':')
+        self.gt_index = fmt.index('GT') if 'GT' in fmt else -1
+        self.fields = f[9:]
+
+    def codes(self, n_cols, cache):
+        """GT_* code of every sample column (a record with fewer fields than the header has columns: the rest are empty = missing)."""
+        gi = self.gt_index
+        if gi < 0:
+            return [GT_MISSING] * n_cols
+        out = []
+        for field in self.fields[:n_cols]:
+            c = cache.get(field) if gi == 0 else None
+            if c is None:
+                sub = field.split(':', gi + 1)
+                c = gt_code(sub[gi]) if gi < len(sub) else GT_MISSING
+                if gi == 0 and len(cache) < 65536:
+                    cache[field] = c
+            out.append(c)
+        out += [GT_MISSING] * (n_cols - len(out))
+        return out
+
+
+def _open_text(path):
+    """Text handle of a plain, gzip or BGZF file, sniffed from the magic bytes (BGZF is a series of gzip members: gzip reads it)."""
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    return gzip.open(path, "rt") if magic == b"\x1f\x8b" else open(path, "r")
+
+
+class VcfFile(object):
+    """Iterator over the records of a VCF text file, with the region query burden testing needs.  `samples`: the header's columns."""
+
+    def __init__(self, path):
+        self.path = path
+        self._fh = _open_text(path)
+        self.samples = None
+        for line in self._fh:
+            if line.startswith('#CHROM'):
+                self.samples = [str(x) for x in line.rstrip('\r\n').split('\t')[9:]]
+                break
+            if not line.startswith('#'):
+                break
+        if self.samples is None:
+            raise ValueError('%s has no #CHROM header line; is this a VCF file?' % path)
+        self._cache = {}
+        self._indexed = {}                # (contig, start, end) -> records whose span meets [start, end), in file order
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        for line in self._fh:
+            if line.rstrip('\r\n') and not line.startswith('#'):
+                return VcfRecord(line)
+        raise StopIteration
+
+    def close(self):
+        self._fh.close()
+
+    def apply(self, rec, d):
+        """read_vcf_var (input.py:455-503) on the dictionary d shared by the records of a burden region: present stays; otherwise the last
+        applied record decides between missing and absent.  Returns the record's name, None if it is skipped."""
+        if rec.skip == VCF_MULTI:
+            sys.stderr.write("Multiple alleles at %s_%d. Skipping\n" % (rec.contig, rec.pos))
+            return None
+        if rec.skip:
+            return None
+        for sample, c in zip(self.samples, rec.codes(len(self.samples), self._cache)):
+            if c == GT_PRESENT:
+                d[sample] = 1
+            elif c == GT_MISSING:
+                if sample not in d:
+                    d[sample] = np.nan
+            elif sample in d and d[sample] != 1:
+                del d[sample]
+        return rec.name
+
+    def prepare(self, intervals):
+        """One pass over the file for all the (contig, start, end) not looked up before: no index file is read."""
+        import bisect
+        todo = [iv for iv in dict.fromkeys(intervals) if iv not in self._indexed]
+        if not todo:
+            return
+        by_contig = {}
+        for iv in todo:
+            self._indexed[iv] = []
+            by_contig.setdefault(iv[0], []).append(iv)
+        starts, longest = {}, {}
+        for c, ivs in by_contig.items():
+            ivs.sort(key=lambda iv: iv[1])
+            starts[c] = [iv[1] for iv in ivs]
+            longest[c] = max(iv[2] - iv[1] for iv in ivs)
+        with _open_text(self.path) as fh:
+            for line in fh:
+                if line.startswith('#') or not line.rstrip('\r\n'):
+                    continue
+                tab = line.index('\t')
+                contig = line[:tab]
+                if contig not in by_contig:
+                    continue
+                f = line.split('\t', 5)
+                a = int(f[1]) - 1
+                b = a + len(f[3])
+                ivs = by_contig[contig]
+                rec = None
+                for j in range(bisect.bisect_left(starts[contig], a - longest[contig]), bisect.bisect_left(starts[contig], b)):
+                    if ivs[j][1] < b and a < ivs[j][2]:
+                        rec = rec or VcfRecord(line)
+                        self._indexed[ivs[j]].append(rec)
+
+    def fetch(self, contig, start, end):
+        """The records whose span [POS-1, POS-1+len(REF)) meets [start, end), in file order (what pysam's fetch returns from the index)."""
+        self.prepare([(contig, start, end)])
+        return self._indexed[(contig, start, end)]
+
+
+_REGION = re.compile(r'^(.+):(\d+)-(\d+)$')
+
+
+def parse_region(region):
+    """'contig:start-end' -> the (contig, start - 1, end) the reference hands to fetch (input.py:394-401), or None."""
+    m = _REGION.match(region)
+    return (m.group(1), int(m.group(2)) - 1, int(m.group(3))) if m else None
+
+
 def open_variant_file(var_type, var_file, burden_file=None, burden_regions=None, uncompressed=False):
     """(handle, sample_order) (input.py:268-299)."""
+    if var_type == "vcf":
+        infile = VcfFile(var_file)
+        if burden_file:
+            load_burden(burden_file, burden_regions)
+        return infile, []
     if var_type == "kmers":
         return (open(var_file) if uncompressed else gzip.open(var_file, 'r')), []
     if var_type == "Rtab":
@@ -153,13 +322,35 @@ def hash_pattern(k):
 def read_variant(infile, p, var_type, burden, burden_regions, uncompressed, all_strains, sample_order,
                  keep_list=None, noparse=False):
     """(eof, k, var_name, kstrains, nkstrains, af, missing) for the next line (input.py:301-454)."""
-    if var_type not in ('kmers', 'Rtab'):
+    if var_type not in ('kmers', 'vcf', 'Rtab'):
         raise ValueError('Variants type not supported')
-    line = infile.readline()
+    if var_type == "vcf":
+        if burden:                                   # one variant per line of the regions file (input.py:355-361)
+            line = burden_regions.popleft() if len(burden_regions) > 0 else None
+        else:
+            line = next(infile, None)
+    else:
+        line = infile.readline()
     if not line or noparse:
         return True, None, None, None, None, None, None
     d = {}
-    if var_type == "kmers":
+    if var_type == "vcf":
+        if not burden:
+            var_name = infile.apply(line, d)
+            if var_name is None or (keep_list is not None and var_name not in keep_list):
+                return False, None, None, None, None, None, None
+        else:
+            var_name, regions = line
+            parsed = [parse_region(r) for r in regions]
+            # the first look-up indexes this line's regions and all those still queued, in one pass over the file
+            infile.prepare([r for r in parsed if r] + [r for r in (parse_region(x) for _, rs in burden_regions for x in rs) if r])
+            for region in parsed:
+                if region is None:
+                    sys.stderr.write("Could not parse region %s\n" % str(region))      # (the reference prints its failed match: None)
+                    continue
+                for rec in infile.fetch(*region):
+                    infile.apply(rec, d)
+    elif var_type == "kmers":
         if not uncompressed:
             line = line.decode()
         var_name = line.split()[0]
@@ -258,7 +449,8 @@ class PackedBlock(object):
 
     def __init__(self, n_samples, capacity):
         self._names, self.patterns, self.afs, self.kstrains, self.nkstrains = [], [], [], [], []
-        self.status = []            # 0 = to engine, 1 = af/missing filtered, 2 = carries missing calls (NaN in k)
+        self.status = []            # 0 = to engine, 1 = af/missing filtered, 2 = carries missing calls (NaN in k),
+                                    # 3 = a VCF record the reader skipped (multi-allelic / FILTER): counted as loaded and pre-filtered, never a row
         self.ks = []                # the dense k only for status 2 (host-side handling of the error path)
         self.row_of = []            # row in self.bits, or -1
         self.names_blob = self.name_off = None     # concatenated names + offsets when the native reader supplied them
@@ -282,7 +474,7 @@ class PackedBlock(object):
 
 
 def iter_packed_blocks(p, var_type, infile, all_strains, sample_order, min_af, max_af, max_missing, uncompressed,
-                       block_size, want_patterns=True):
+                       block_size, want_patterns=True, burden=False, burden_regions=None):
     """Parse `block_size` variants at a time into a PackedBlock (same filters as iter_variants / load_var_block)."""
     n = len(p)
     while True:
@@ -290,12 +482,16 @@ def iter_packed_blocks(p, var_type, infile, all_strains, sample_order, min_af, m
         nrow = 0
         eof = False
         for _ in range(block_size):
-            eof, k, name, ks, nks, af, missing = read_variant(infile, p, var_type, False, None, uncompressed, all_strains,
+            eof, k, name, ks, nks, af, missing = read_variant(infile, p, var_type, burden, burden_regions, uncompressed, all_strains,
                                                               sample_order)
             if eof:
                 break
-            blk.names.append(name); blk.afs.append(af); blk.kstrains.append(ks); blk.nkstrains.append(nks)
             blk.last_k = k
+            if name is None:                     # a skipped VCF record (input.py:608, :693: `k is None`)
+                blk.names.append(''); blk.afs.append(np.nan); blk.kstrains.append(_NO_STRAINS); blk.nkstrains.append(_NO_STRAINS)
+                blk.patterns.append(None); blk.status.append(3); blk.row_of.append(-1); blk.ks.append(None)
+                continue
+            blk.names.append(name); blk.afs.append(af); blk.kstrains.append(ks); blk.nkstrains.append(nks)
             if k is None or not (min_af <= af <= max_af) or missing > max_missing:
                 blk.patterns.append(hash_pattern(k) if k is not None else None)
                 blk.status.append(1); blk.row_of.append(-1); blk.ks.append(None)
@@ -369,6 +565,240 @@ class NativeKmerReader(object):
         """(names, bits, counts) per block, names decoded to str."""
         for bits, counts, blob, off in self.raw_blocks():
             yield [blob[off[v]:off[v + 1]].decode() for v in range(counts.shape[0])], bits, counts
+
+
+class NativeVcfReader(object):
+    """Blocks of VCF records through libseerhip's reader (sh_vcf_*: csrc/vcf_reader.cpp on the host, k_vcf_gt_pack on the device): per record
+    the name, the skip reason, POS, len(REF), the contig and the packed present / missing rows over `sample_names`.
+    engine: the Engine whose device and stream the reader uses; None selects the library's host restatement of the kernel (measurements and
+    checks without a device -- the command line always passes its engine)."""
+
+    def __init__(self, path, sample_names, engine=None, block_size=3000):
+        import ctypes as C
+        from . import _abi
+        self._C, self._abi = C, _abi
+        self._lib = _abi.load()
+        self.samples = [str(x) for x in sample_names]
+        self.n = len(self.samples)
+        self._engine = engine                               # (kept alive: the reader holds its context)
+        arr = (C.c_char_p * self.n)(*[x.encode() for x in self.samples])
+        h = self._lib.sh_vcf_open(engine._h if engine is not None else None, str(path).encode(), arr, self.n)
+        if not h:
+            raise IOError(self._lib.sh_last_error().decode())
+        self._h = C.c_void_p(h)
+        self.block_size = int(block_size)
+        self.row_bytes = row_bytes_for(self.n)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sh_vcf_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        C = self._C
+        mode, ncols, ncontigs = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._abi.check(self._lib.sh_vcf_info(self._h, C.byref(mode), C.byref(ncols), C.byref(ncontigs)))
+        return {"container": ("plain", "gzip", "bgzf")[mode.value], "columns": ncols.value, "contigs": ncontigs.value}
+
+    def stats(self):
+        C = self._C
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._abi.check(self._lib.sh_vcf_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"sample_bytes": a.value, "records": b.value, "launches": c.value}
+
+    def contig(self, i):
+        return self._lib.sh_vcf_contig(self._h, int(i)).decode()
+
+    def raw_blocks(self):
+        """dict per block: blob / off (names), skip, pos, ref_len, contig, present, missing (packed rows), n_present, n_missing."""
+        C = self._C
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        bs = self.block_size
+        while True:
+            skip = np.zeros(bs, dtype=np.int32); pos = np.zeros(bs, dtype=np.int64); ref_len = np.zeros(bs, dtype=np.int32)
+            contig = np.zeros(bs, dtype=np.int32); n_p = np.zeros(bs, dtype=np.int32); n_m = np.zeros(bs, dtype=np.int32)
+            present = np.zeros((bs, self.row_bytes), dtype=np.uint8); missing = np.zeros((bs, self.row_bytes), dtype=np.uint8)
+            nv = self._lib.sh_vcf_next(self._h, bs, skip.ctypes.data_as(i32), pos.ctypes.data_as(i64), ref_len.ctypes.data_as(i32),
+                                       contig.ctypes.data_as(i32), present.ctypes.data_as(self._abi.c_u8p), missing.ctypes.data_as(self._abi.c_u8p),
+                                       self.row_bytes, n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32))
+            if nv < 0:
+                raise IOError(self._lib.sh_last_error().decode())
+            if nv == 0:
+                return
+            blob_p, off_p = C.c_void_p(0), C.c_void_p(0)
+            nb = self._lib.sh_vcf_names(self._h, C.byref(blob_p), C.byref(off_p))
+            blob = C.string_at(blob_p.value, nb) if nb > 0 else b""
+            off = np.frombuffer(C.string_at(off_p.value, 8 * (nv + 1)), dtype=np.int64).copy()
+            yield {"blob": blob, "off": off, "skip": skip[:nv], "pos": pos[:nv], "ref_len": ref_len[:nv], "contig": contig[:nv],
+                   "present": present[:nv], "missing": missing[:nv], "n_present": n_p[:nv], "n_missing": n_m[:nv]}
+
+
+def _vcf_packed_block(n, samples, order, names, skip, present, missing, n_present, n_missing, min_af, max_af, max_missing, want_patterns,
+                      messages=None):
+    """The PackedBlock iter_packed_blocks builds from read_variant's tuples, from the native reader's rows instead: same names, af, sample
+    lists, statuses, dense k for rows with missing calls, patterns, and the same lines on stderr in the same order.
+    messages[i]: lines to write before record i's own (burden: what applying its regions said)."""
+    nv = len(names)
+    blk = PackedBlock(n, 0)
+    dense_p = np.unpackbits(present, axis=1, bitorder="little")[:, :n]
+    dense_m = np.unpackbits(missing, axis=1, bitorder="little")[:, :n]
+    rows = []
+    for i in range(nv):
+        if messages is not None:
+            sys.stderr.write(messages[i])
+        if skip[i]:
+            blk.last_k = None
+            blk.names.append(''); blk.afs.append(np.nan); blk.kstrains.append(_NO_STRAINS); blk.nkstrains.append(_NO_STRAINS)
+            blk.patterns.append(None); blk.status.append(3); blk.row_of.append(-1); blk.ks.append(None)
+            continue
+        nm = int(n_missing[i])
+        cnt = int(n_present[i]) + nm
+        af, miss = float(cnt) / n, float(nm) / n
+        if cnt == 0:
+            sys.stderr.write("No observations of " + names[i] + " in selected samples\n")
+        carried = (dense_p[i] | dense_m[i]).astype(bool)
+        ks = [samples[j] for j in order if carried[j]]
+        nks = [samples[j] for j in order if not carried[j]]
+        if nm:
+            k = dense_p[i].astype(np.float64)
+            k[dense_m[i].astype(bool)] = np.nan
+        else:
+            k = dense_p[i].astype(np.int64)
+        blk.last_k = k
+        blk.names.append(names[i]); blk.afs.append(af); blk.kstrains.append(ks); blk.nkstrains.append(nks)
+        if not (min_af <= af <= max_af) or miss > max_missing:
+            blk.patterns.append(hash_pattern(k)); blk.status.append(1); blk.row_of.append(-1); blk.ks.append(None)
+            continue
+        blk.patterns.append(hash_pattern(k) if want_patterns else b'')
+        if nm:
+            blk.status.append(2); blk.row_of.append(-1); blk.ks.append(k)
+            continue
+        blk.status.append(0); blk.row_of.append(len(rows)); blk.ks.append(None)
+        rows.append(i)
+    blk.bits = np.ascontiguousarray(present[rows]) if rows else np.zeros((0, present.shape[1]), dtype=np.uint8)
+    return blk
+
+
+def _merged_intervals(regions):
+    """{contig: (starts, ends)} of the union of the (contig, start, end) given, as sorted disjoint intervals."""
+    by = {}
+    for c, s_, e_ in regions:
+        by.setdefault(c, []).append((s_, e_))
+    out = {}
+    for c, ivs in by.items():
+        ivs.sort()
+        merged = [list(ivs[0])]
+        for s_, e_ in ivs[1:]:
+            if s_ <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], e_)
+            else:
+                merged.append([s_, e_])
+        out[c] = (np.array([m_[0] for m_ in merged], dtype=np.int64), np.array([m_[1] for m_ in merged], dtype=np.int64))
+    return out
+
+
+def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, burden_regions=None):
+    """The PackedBlock stream of iter_packed_blocks(p, 'vcf', ...) fed by the native reader.  burden_regions: the (name, [region, ...]) list
+    load_burden fills -- one variant per entry: the file is read once, the rows of the records that lie in any region are kept, and
+    k_burden_fold (sh_burden_fold) combines each variant's records on the device."""
+    samples = [str(x) for x in p.index]
+    order = sorted(range(len(samples)), key=lambda i: samples[i])
+    n = len(samples)
+    reader = NativeVcfReader(path, samples, engine, block_size)
+
+    def multi_message(contig, pos):
+        return "Multiple alleles at %s_%d. Skipping\n" % (contig, pos)
+
+    def plain():
+        for rb in reader.raw_blocks():
+            blob, off = rb["blob"], rb["off"]
+            names = [blob[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)]
+            msgs = [multi_message(reader.contig(rb["contig"][i]), int(rb["pos"][i])) if rb["skip"][i] == VCF_MULTI else "" for i in range(len(names))]
+            yield _vcf_packed_block(n, samples, order, names, rb["skip"], rb["present"], rb["missing"], rb["n_present"], rb["n_missing"],
+                                    min_af, max_af, max_missing, want_patterns, msgs)
+
+    def burden():
+        import ctypes as C
+        from . import _abi
+        variants = list(burden_regions)
+        parsed = [[parse_region(r) for r in regions] for _, regions in variants]
+        union = _merged_intervals([r for rs in parsed for r in rs if r])
+        # pass over the file: the records that meet any region stay (rows, span, skip reason), the rest are dropped
+        keep = {"contig": [], "a": [], "b": [], "skip": [], "present": [], "missing": []}
+        for rb in reader.raw_blocks():
+            a = rb["pos"] - 1
+            b = a + rb["ref_len"]
+            hit = np.zeros(a.shape[0], dtype=bool)
+            for cid in np.unique(rb["contig"]):
+                iv = union.get(reader.contig(cid))
+                if iv is None:
+                    continue
+                sel = rb["contig"] == cid
+                j = np.searchsorted(iv[0], b[sel], side="left") - 1             # the last interval that starts before the record ends
+                hit[sel] = (j >= 0) & (a[sel] < iv[1][np.maximum(j, 0)])
+            if hit.any():
+                keep["contig"].append(np.array([reader.contig(c) for c in rb["contig"][hit]], dtype=object))
+                keep["a"].append(a[hit]); keep["b"].append(b[hit]); keep["skip"].append(rb["skip"][hit])
+                keep["present"].append(rb["present"][hit]); keep["missing"].append(rb["missing"][hit])
+        rb_ = reader.row_bytes
+        if keep["a"]:
+            kc = np.concatenate(keep["contig"]); ka = np.concatenate(keep["a"]); kb = np.concatenate(keep["b"]); ksk = np.concatenate(keep["skip"])
+            kp = np.ascontiguousarray(np.concatenate(keep["present"])); km = np.ascontiguousarray(np.concatenate(keep["missing"]))
+        else:
+            kc = np.zeros(0, dtype=object); ka = kb = np.zeros(0, dtype=np.int64); ksk = np.zeros(0, dtype=np.int32)
+            kp = km = np.zeros((0, rb_), dtype=np.uint8)
+        by_contig = {}
+        for c in set(kc.tolist()):
+            idx = np.nonzero(kc == c)[0]
+            o = np.argsort(ka[idx], kind="stable")
+            by_contig[c] = (idx[o], ka[idx][o], int((kb[idx] - ka[idx]).max()))
+        lib = _abi.load()
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        for v0 in range(0, len(variants), block_size):
+            chunk = range(v0, min(len(variants), v0 + block_size))
+            msgs, csr_off, csr_idx = [], [0], []
+            for v in chunk:
+                msg = ""
+                for region in parsed[v]:
+                    if region is None:
+                        msg += "Could not parse region %s\n" % str(region)
+                        continue
+                    contig, start, end = region
+                    if contig not in by_contig:
+                        continue
+                    idx, a_sorted, longest = by_contig[contig]
+                    cand = idx[np.searchsorted(a_sorted, start - longest, side="left"):np.searchsorted(a_sorted, end, side="left")]
+                    cand = np.sort(cand[kb[cand] > start])                   # file order
+                    for rec in cand:
+                        if ksk[rec] == VCF_MULTI:
+                            msg += multi_message(contig, int(ka[rec]) + 1)
+                        if ksk[rec] == VCF_KEPT:
+                            csr_idx.append(int(rec))
+                msgs.append(msg)
+                csr_off.append(len(csr_idx))
+            nvar = len(chunk)
+            off_a = np.array(csr_off, dtype=np.int64); idx_a = np.array(csr_idx if csr_idx else [0], dtype=np.int32)
+            out_p = np.zeros((nvar, rb_), dtype=np.uint8); out_m = np.zeros((nvar, rb_), dtype=np.uint8)
+            n_p = np.zeros(nvar, dtype=np.int32); n_m = np.zeros(nvar, dtype=np.int32)
+            if engine is None:
+                raise ValueError("burden regions need the device (sh_burden_fold)")
+            _abi.check(lib.sh_burden_fold(engine._h, kp.ctypes.data_as(_abi.c_u8p), km.ctypes.data_as(_abi.c_u8p), rb_, kp.shape[0], off_a.ctypes.data_as(i64),
+                                          idx_a.ctypes.data_as(i32), nvar, out_p.ctypes.data_as(_abi.c_u8p), out_m.ctypes.data_as(_abi.c_u8p),
+                                          n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32)))
+            yield _vcf_packed_block(n, samples, order, [variants[v][0] for v in chunk], np.zeros(nvar, dtype=np.int32), out_p, out_m, n_p, n_m,
+                                    min_af, max_af, max_missing, want_patterns, msgs)
+
+    try:
+        for blk in (burden() if burden_regions is not None else plain()):
+            yield blk
+    finally:
+        reader.close()
 
 
 def prefetched(iterable, depth=2):

@@ -1,0 +1,125 @@
+"""Rates of the VCF readers on a generated call set: N = 5000 phenotyped samples among 5200 columns (tests/_vcf_text.py: 1-byte and 20-byte
+sample fields, GT first or second in FORMAT, ~3 % missing, multi-allelic and filtered records), tiled to at least --gb of text, BGZF.
+
+  python tools/bench_vcf_reader.py --dir /tmp/vcfbench --gb 1.0                       # (a) Python reader, (b) native end to end, (d) host tokeniser
+  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_vcf_reader.py --dir /tmp/vcfbench --gb 1.0 --only native
+  python tools/bench_vcf_reader.py --kernel-stats OUT                                 # (c) k_vcf_gt_pack alone, from the trace of the run above
+
+(b) and (d) read the whole file twice and report the second pass (the first pass also pays the page cache and the pinned slabs); (a) reads the
+first --python-records records.  (d) is the same reader with the kernel's work done by shvcf::host_gt_pack on the host pool (16 threads under
+the GPU host's quota).  Prints one JSON line per measurement."""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_MEASURED, HBM_SPEC = 6.29e12, 8.0e12          # bytes/s: float4 copy measured, and the specification
+
+
+def make_file(d, gb):
+    from _vcf_text import bgzf_bytes, generated_vcf
+    os.makedirs(d, exist_ok=True)
+    path, meta = os.path.join(d, "gen.vcf.gz"), os.path.join(d, "meta.json")
+    if os.path.exists(path) and os.path.exists(meta) and json.load(open(meta))["gb"] == gb:
+        return path, json.load(open(meta))
+    text, pheno, cols = generated_vcf(n_pheno=5000, n_cols=5200, n_records=2000, seed=7, missing=0.03)
+    head_end = text.index(b"\n", text.index(b"#CHROM")) + 1
+    body = text[head_end:]
+    tiles = max(1, int(-(-gb * 1e9 // len(body))))
+    with open(path, "wb") as f:
+        f.write(bgzf_bytes(text[:head_end], level=1)[:-28])
+        comp = bgzf_bytes(body, level=1)[:-28]                   # (without the end-of-file member)
+        for _ in range(tiles):
+            f.write(comp)
+        f.write(bgzf_bytes(b"")[-28:])
+    with open(os.path.join(d, "first.vcf"), "wb") as f:
+        f.write(text)
+    m = {"gb": gb, "records": 2000 * tiles, "text_bytes": head_end + tiles * len(body), "file_bytes": os.path.getsize(path), "samples": pheno}
+    json.dump(m, open(meta, "w"))
+    return path, m
+
+
+def kernel_stats(out_dir):
+    rows = []
+    for f in glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True):
+        rows += list(csv.DictReader(open(f)))
+    for r in rows:
+        if "k_vcf_gt_pack" in r["Name"]:
+            return {"kernel": "k_vcf_gt_pack", "calls": int(r["Calls"]), "total_s": float(r["TotalDurationNs"]) * 1e-9, "mean_us": float(r["AverageNs"]) * 1e-3}
+    raise SystemExit("no k_vcf_gt_pack row under " + out_dir)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", default="/tmp/vcfbench")
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--only", default=None, choices=["python", "native", "host"])
+    ap.add_argument("--python-records", type=int, default=400)
+    ap.add_argument("--block", type=int, default=3000)
+    ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--traced-json", default=None, help="with --kernel-stats: the JSON line the traced run printed (its sample bytes, two passes)")
+    o = ap.parse_args()
+    if o.kernel_stats:
+        k = kernel_stats(o.kernel_stats)
+        if o.traced_json:
+            line = json.loads(open(o.traced_json).read().strip().splitlines()[-1])
+            k["sample_bytes"] = 2 * line["sample_bytes"]                 # the traced run reads the file twice
+            k["records"] = 2 * line["records"]
+            k["records_per_s"] = k["records"] / k["total_s"]
+            k["bytes_per_s"] = k["sample_bytes"] / k["total_s"]
+            k["share_of_measured_hbm_copy_rate"] = k["bytes_per_s"] / HBM_MEASURED
+            k["share_of_hbm_spec"] = k["bytes_per_s"] / HBM_SPEC
+        print(json.dumps(k))
+        return
+    path, meta = make_file(o.dir, o.gb)
+    samples = meta["samples"]
+    base = {"records": meta["records"], "text_GB": meta["text_bytes"] / 1e9, "file_MB": meta["file_bytes"] / 1e6, "n_samples": len(samples), "columns": 5200}
+    if o.only in (None, "python"):
+        import contextlib
+        import io
+        from pyseer_amd.input import VcfFile
+        f = VcfFile(os.path.join(o.dir, "first.vcf"))
+        t0 = time.perf_counter()
+        n = 0
+        with contextlib.redirect_stderr(io.StringIO()):
+            for rec in f:
+                f.apply(rec, {})
+                n += 1
+                if n >= o.python_records:
+                    break
+        dt = time.perf_counter() - t0
+        print(json.dumps(dict(base, reader="python (plain text, first %d records)" % n, seconds=dt, records_per_s=n / dt)))
+    for which in ("native", "host"):
+        if o.only not in (None, which):
+            continue
+        from pyseer_amd.input import NativeVcfReader
+        eng = None
+        if which == "native":
+            from pyseer_amd.engine import Engine
+            eng = Engine(len(samples))
+        for rep in range(2):
+            r = NativeVcfReader(path, samples, eng, o.block)
+            t0 = time.perf_counter()
+            n = npres = 0
+            for rb in r.raw_blocks():
+                n += len(rb["skip"]); npres += int(rb["n_present"].sum())
+            dt = time.perf_counter() - t0
+            st = r.stats()
+            r.close()
+        assert n == meta["records"], (n, meta["records"])
+        print(json.dumps(dict(base, reader=("native, sample columns on the device" if eng else "native reader, host tokeniser (host pool)"), seconds=dt,
+                              records_per_s=n / dt, text_GB_per_s=meta["text_bytes"] / 1e9 / dt, sample_bytes=st["sample_bytes"], launches=st["launches"],
+                              present_calls=npres, block=o.block)))
+        if eng is not None:
+            eng.close()
+
+
+if __name__ == "__main__":
+    main()
