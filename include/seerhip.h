@@ -362,6 +362,57 @@ int         sh_vcf_stats(sh_vcf *r, int64_t *sample_bytes, int64_t *records, int
 int         sh_burden_fold(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t n_records, const int64_t *csr_off,
                            const int32_t *csr_idx, int64_t n_variants, uint8_t *out_present, uint8_t *out_missing, int32_t *n_present, int32_t *n_missing);
 
+/* ---------------------------------------------------------------------------------------------
+ * Whole-genome elastic net (csrc/enet_kernels.hip + csrc/enet_api.inc; replaces pyseer/enet.py load_all_vars :33-118, correlation_filter
+ * :379-421 and the cvglmnet call of fit_enet :177-185).  One bit matrix of every variant that passed the filters stays on the device; the full
+ * fit and each cross-validation fold are that matrix with other sample weights (a held-out sample has weight 0).
+ *   begin / append / end: reserve `capacity` rows of row_bytes (layout of sh_lmm_batch), add V rows.  flip[v] != 0 (may be NULL) stores the
+ *     row in the minor-allele coding of enet.py:95-106: by its absences, a missing call (the `missing` rows, may be NULL) being 0 either way.
+ *   correlations: |cor(row, y)| of enet.py:398-418 for every row, NaN for a row without carriers.  The quantile cut is the caller's.
+ *   keep: compact the matrix to rows idx[0 .. n_keep) (ascending or not); get_rows: copy rows idx[] out (host pointer), e.g. the selected
+ *     variants for the per-variant engine, so that no input is read twice (enet.py:424 find_enet_selected reads it again).
+ *   fit: y, weights (NULL = 1; normalised to sum 1), n_cov dense covariate columns (covariates[k * n_samples + i], penalised like variants,
+ *     enet.py:173-174), fold_id[i] in [0, n_folds) (n_folds = 0: no cross-validation), family 0 gaussian / 1 binomial, alpha in [0, 1].
+ *     Minimises glmnet's objective with standardize = intercept = TRUE over a path of n_lambda penalties from lambda_max down (DESIGN.md
+ *     section 12 states every rule); arrays of sh_enet_out are the caller's, of opts->n_lambda entries (fold_dev: n_folds x n_lambda,
+ *     row f at f * opts->n_lambda; beta: n_cov + rows), any may be NULL.  out->n_lambda = values fitted before the path ended,
+ *     i_min = argmin cvm (-1 without folds), beta0 / beta = the full fit at i_min (at the last value without folds), original scale.
+ *   betas_at: the solution of problem 0 (full fit) or 1 + k (fold k held out) at lambda i of the last fit; eta_at: the full fit's linear
+ *     predictor of every sample there.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sh_enet_opts {
+    int32_t n_lambda;          /* 0 = 100 */
+    int32_t max_sweeps;        /* sweeps per launch before the host looks again; 0 = 100000.  A binomial launch that ends on this budget
+                                * restarts with a fresh IRLS step, so the 25-step IRLS cap counts per launch and the iterates (not the
+                                * optimum) depend on this value: leave it at 0 unless a launch must stay short */
+    int32_t state_in_global;   /* != 0: keep the per-sample state in global memory even where it fits the LDS */
+    int32_t reserved;
+    double  thresh;            /* glmnet's thresh: a solve ends when the largest xv_j delta_j^2 of a sweep < thresh x null deviance; 0 = 1e-7 */
+    double  lambda_min_ratio;  /* 0 = glmnet's default: 1e-2 if n_samples < columns else 1e-4 */
+    const double *lambda_seq;  /* NULL, or n_lambda decreasing penalties to use instead of the computed sequence (glmnet's `lambda`) */
+} sh_enet_opts;
+typedef struct sh_enet_out {
+    int32_t n_lambda, i_min, kkt_rounds, state_in_lds;
+    int64_t cd_sweeps, cd_steps;   /* sweeps and coordinate steps of k_enet_cd, summed over problems */
+    double  beta0, cvm_min;
+    double *lambda, *cvm, *cvsd, *dev_ratio, *fold_dev, *fold_weight, *beta;
+    int32_t *nzero;
+} sh_enet_out;
+int     sh_enet_begin(sh_ctx *ctx, int64_t row_bytes, int64_t capacity);
+int     sh_enet_append(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, const uint8_t *flip, int64_t V);
+int64_t sh_enet_rows(sh_ctx *ctx);
+int     sh_enet_correlations(sh_ctx *ctx, const double *y, double *out_abs_cor);
+/* out[f * rows + j] = sum over the carriers i of row j of vectors[f * n_samples + i] (k_enet_grad, 16 vectors a pass): the pass behind the
+ * weighted means, lambda_max, the strong rule and the KKT check, callable on its own (tests, measurements) */
+int     sh_enet_carrier_sums(sh_ctx *ctx, const double *vectors, int n_vectors, double *out);
+int     sh_enet_keep(sh_ctx *ctx, const int64_t *idx, int64_t n_keep);
+int     sh_enet_get_rows(sh_ctx *ctx, const int64_t *idx, int64_t n, uint8_t *rows);
+int     sh_enet_fit(sh_ctx *ctx, const double *y, const double *weights, const double *covariates, int n_cov, const int32_t *fold_id, int n_folds,
+                    int family, double alpha, const sh_enet_opts *opts, sh_enet_out *out);
+int     sh_enet_betas_at(sh_ctx *ctx, int problem, int i_lambda, double *beta0, double *beta);
+int     sh_enet_eta_at(sh_ctx *ctx, int i_lambda, double *eta);
+int     sh_enet_end(sh_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,11 +123,22 @@ def get_options(argv=None):
     asc = parser.add_argument_group('Association options')
     asc.add_argument('--continuous', action='store_true', default=False, help='Force continuous phenotype')
     asc.add_argument('--lmm', action='store_true', default=False, help='Use random instead of fixed effects')
-    asc.add_argument('--wg', default=None, help='(not supported by this build)')
+    asc.add_argument('--wg', default=None, help='Use a whole genome model for association and prediction: enet (rf and blup are not built)')
     asc.add_argument('--lineage', action='store_true', help='Report lineage effects')
     asc.add_argument('--lineage-clusters', help='Custom clusters to use as lineages [Default: MDS components]')
     asc.add_argument('--lineage-file', default="lineage_effects.txt", help='File to write lineage association to')
+    wg = parser.add_argument_group('Whole genome options')
+    wg.add_argument('--sequence-reweighting', action='store_true', help='Use --lineage-clusters to downweight sequences.')
+    wg.add_argument('--save-vars', help='(not built: pickles of the reference)')
+    wg.add_argument('--load-vars', help='(not built: pickles of the reference)')
+    wg.add_argument('--save-model', help='(not built: pickles of the reference)')
+    wg.add_argument('--save-predictions', default=None, help='File to save predictions to in TSV format [Default: do not save predictions]')
+    wg.add_argument('--alpha', type=float, default=0.0069, help='Set the mixing between l1 and l2 penalties [Default: 0.0069]')
+    wg.add_argument('--n-folds', type=int, default=10, help='Number of folds cross-validation to perform [Default: 10]')
+    wg.add_argument('--enet-seed', type=int, default=1, help='Seed of the random fold assignment (numpy.random.default_rng) [Default: 1]')
+    wg.add_argument('--enet-thresh', type=float, default=1e-7, help="Convergence threshold of the coordinate descent (glmnet's thresh) [Default: 1e-7]")
     fi = parser.add_argument_group('Filtering options')
+    fi.add_argument('--cor-filter', type=float, default=0.25, help='Correlation filter for elastic net (phenotype/variant correlation quantile at which to start keeping variants) [Default: 0.25]')
     fi.add_argument('--min-af', type=float, default=0.01, help='Minimum AF [Default: 0.01]')
     fi.add_argument('--max-af', type=float, default=0.99, help='Maximum AF [Default: 0.99]')
     fi.add_argument('--max-missing', type=float, default=0.05, help='Maximum missing (vcf/Rtab) [Default: 0.05]')
@@ -195,8 +206,20 @@ def main(argv=None):
         _die('Burden test can only be performed with VCF input\n')
     if options.vcf and (options.gpus is not None or options.save_packed or options.load_packed or options.packed_cache or options.packed_part):
         _die('--gpus and the packed cache (--save-packed / --load-packed / --packed-cache / --packed-part) are not available with --vcf\n')
+    if options.lmm and options.wg:
+        _die('Choose only one alternative model. Either --lmm, --wg or neither\n')
+    if options.wg and options.wg != 'enet':
+        _die("Whole-genome model '%s' is not built in pyseer_amd (only --wg enet is)\n" % options.wg)
     if options.wg:
-        _die('Whole-genome models (--wg) are out of scope for pyseer_amd\n')
+        for name_, val_ in (('--save-vars', options.save_vars), ('--load-vars', options.load_vars), ('--save-model', options.save_model)):
+            if val_:
+                _die('%s writes pickles of reference-internal objects and is not built in pyseer_amd\n' % name_)
+        if options.gpus is not None or options.packed_part:
+            _die('--wg enet runs on one device: --gpus and --packed-part are not available with it\n')
+        if options.load_packed or options.save_packed or options.packed_cache or (options.kmers and len(options.kmers) > 1):
+            _die('--wg enet reads one variant file through the Python readers: the packed cache and several --kmers files are not available with it\n')
+        if not (0.0 <= options.alpha <= 1.0):
+            _die('--alpha must lie in [0, 1]\n')
     if options.max_dimensions < 1:
         _die('Minimum number of dimensions after MDS is 1\n')
     if options.lmm and not options.similarity and not options.load_lmm:
@@ -207,15 +230,21 @@ def main(argv=None):
             _die('Unless performing a lineage analysis with random effects\n')
         if options.lmm and not (options.distances or options.load_m) and options.lineage:
             _die('Must also provide a distance matrix to report lineage effects\n')
-        if not options.lmm and not options.distances and not options.load_m:
+        if not options.lmm and not options.wg and not options.distances and not options.load_m:
             _die('Option --no-distances must be used when no distance matrix is provided\n')
     else:
         if options.distances or options.load_m:
             _die('Cannot use --no-distances with --distances or --load-m\n')
-        if not options.lmm and not options.lineage_clusters and options.lineage:
+        if not options.lmm and not options.wg and not options.lineage_clusters and options.lineage:
             _die('Must provide a lineage clusters file when --no-distances and --lineage are used together in fixed-effects mode\n')
         if options.lmm:
             _die('Cannot use --no-distances with --lmm\n')
+    if options.wg and options.sequence_reweighting and (not options.lineage_clusters or options.lineage):
+        sys.stderr.write("Using sequence reweighting requires clusters to weight with.\n")
+        _die("Provide these with --lineage-clusters. Incompatible with --lineage.\n")
+    if options.wg and options.output_patterns:
+        sys.stderr.write("Whole genome model does not produce patterns.\n")
+        _die("Re-run without --output-patterns.\n")
     if options.block_size < 1:
         _die('Block size must be at least 1\n')
     warnings.filterwarnings('ignore')
@@ -238,7 +267,8 @@ def main(argv=None):
 
     m = np.empty(shape=(0, 0))
     null_fit = firth_null = None
-    if (options.lineage and not options.lineage_clusters) or not options.lmm:
+    enet_seer = bool(options.wg and options.distances or options.load_m)          # pyseer/__main__.py:334-336
+    if (options.lineage and not options.lineage_clusters) or enet_seer or not (options.lmm or options.wg):
         if not options.no_distances:
             if options.load_m and os.path.isfile(options.load_m):
                 mdf = pd.read_pickle(options.load_m)
@@ -269,6 +299,7 @@ def main(argv=None):
     lineage_dict = None
     if options.lineage_clusters:
         lineage_clusters, lineage_dict = load_lineage(options.lineage_clusters, p)
+    clusters_full, dict_full = (np.copy(lineage_clusters), list(lineage_dict)) if options.lineage_clusters else (None, lineage_dict)
     if options.lineage:
         from scipy.stats import norm
         lineage_wald = {}
@@ -293,6 +324,24 @@ def main(argv=None):
             lineage_out.write("\t".join(["lineage", "wald_test", "p-value"]) + "\n")
             for lineage, wald in sorted(lineage_wald.items(), key=lambda kv: kv[1], reverse=True):
                 lineage_out.write("\t".join([lineage, str(wald), str(2 * (1 - norm.cdf(wald)))]) + "\n")
+
+    if options.wg:
+        from . import enet as _enet
+        wt_ = globals().get("_warm_thread")
+        if wt_ is not None:
+            wt_.join()
+        if not options.lineage:
+            lineage_dict = None
+        try:
+            prefilter_, tested_, printed_ = _enet.run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_dict, clusters_full,
+                                                          dict_full, enet_seer, sys.stdout, sys.stderr)
+        except ValueError as ex_:
+            _die(str(ex_) + "\n")
+        sys.stderr.write('%d loaded variants\n' % (prefilter_ + tested_))
+        sys.stderr.write('%d pre-filtered variants\n' % prefilter_)
+        sys.stderr.write('%d tested variants\n' % tested_)
+        sys.stderr.write('%d printed variants\n' % printed_)
+        return
 
     from .engine import Engine
 

@@ -105,7 +105,34 @@ SIGNATURES = {
     "sh_vcf_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sh_burden_fold": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, c_u8p, c_u8p,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # the whole-genome elastic net (csrc/enet_kernels.hip, csrc/enet_api.inc); the structs are EnetOpts / EnetOut below
+    "sh_enet_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "sh_enet_append": (C.c_int, [C.c_void_p, c_u8p, c_u8p, c_u8p, C.c_int64]),
+    "sh_enet_rows": (C.c_int64, [C.c_void_p]),
+    "sh_enet_correlations": (C.c_int, [C.c_void_p, c_dp, c_dp]),
+    "sh_enet_carrier_sums": (C.c_int, [C.c_void_p, c_dp, C.c_int, c_dp]),
+    "sh_enet_keep": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]),
+    "sh_enet_get_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, c_u8p]),
+    "sh_enet_fit": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "sh_enet_betas_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_dp]),
+    "sh_enet_eta_at": (C.c_int, [C.c_void_p, C.c_int, c_dp]),
+    "sh_enet_end": (C.c_int, [C.c_void_p]),
 }
+
+
+class EnetOpts(C.Structure):
+    """sh_enet_opts"""
+    _fields_ = [("n_lambda", C.c_int32), ("max_sweeps", C.c_int32), ("state_in_global", C.c_int32), ("reserved", C.c_int32),
+                ("thresh", C.c_double), ("lambda_min_ratio", C.c_double), ("lambda_seq", c_dp)]
+
+
+class EnetOut(C.Structure):
+    """sh_enet_out"""
+    _fields_ = [("n_lambda", C.c_int32), ("i_min", C.c_int32), ("kkt_rounds", C.c_int32), ("state_in_lds", C.c_int32),
+                ("cd_sweeps", C.c_int64), ("cd_steps", C.c_int64), ("beta0", C.c_double), ("cvm_min", C.c_double),
+                ("lambda_", c_dp), ("cvm", c_dp), ("cvsd", c_dp), ("dev_ratio", c_dp), ("fold_dev", c_dp), ("fold_weight", c_dp), ("beta", c_dp),
+                ("nzero", C.POINTER(C.c_int32))]
+
 
 _lib = None
 

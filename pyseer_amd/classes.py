@@ -7,6 +7,9 @@ LMM = namedtuple('LMM', ['kmer', 'pattern', 'af', 'prep', 'pvalue', 'kbeta', 'bs
 Seer = namedtuple('Seer', ['kmer', 'pattern', 'af', 'prep', 'pvalue', 'kbeta', 'bse', 'intercept', 'betas',
                            'max_lineage', 'kstrains', 'nkstrains', 'notes', 'prefilter', 'filter'])
 
+# --wg enet (pyseer/classes.py Enet)
+Enet = namedtuple('Enet', ['kmer', 'af', 'prep', 'pvalue', 'kbeta', 'max_lineage', 'kstrains', 'nkstrains', 'notes'])
+
 # bit order of the engine's flags word (include/seerhip.h SH_NOTE_*)
 NOTE_ORDER = ('af-filter', 'pre-filtering-failed', 'bad-chisq', 'high-bse', 'perfectly-separable-data',
               'matrix-inversion-error', 'firth-fail', 'missing-data-error', 'lrt-filtering-failed')

@@ -22,6 +22,7 @@
 #include "lmm_params.h"
 #include "vcf_kernels.h"
 #include "vcf_reader.h"
+#include "enet_params.h"
 extern "C" {
 hipError_t shk_sim_accumulate(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, double min_af, double max_af,
                               int af_on, uint64_t *keep, uint64_t *S, int NS, unsigned long long *Kacc);
@@ -55,6 +56,13 @@ int64_t format_records_samples(const char *, const int64_t *, const int32_t *, i
                                const int64_t *, const int32_t *);
 hipError_t shk_job_patterns(hipStream_t, const uint64_t *, int64_t, int64_t, int, const uint32_t *, int *, long long *, uint32_t *, char *, char *);
 #define JOB_ROWS_PER_BLOCK_HOST 1024
+// enet_kernels.hip
+hipError_t shk_enet_store(hipStream_t, const uint8_t *, const uint8_t *, const uint8_t *, int64_t, int, int, uint64_t *);
+hipError_t shk_enet_gather(hipStream_t, const uint64_t *, const int64_t *, int64_t, int, uint64_t *);
+hipError_t shk_enet_moments(hipStream_t, const uint64_t *, int64_t, int, int, const double *, double, double *);
+hipError_t shk_enet_grad(hipStream_t, const uint64_t *, int64_t, int, const double *, int64_t, int, double *, int64_t);
+size_t shk_enet_cd_lds_bytes(int, int);
+hipError_t shk_enet_cd(hipStream_t, const struct EnetCdArgs *, int);
 }
 #include "glm_api.inc"
 
@@ -91,6 +99,7 @@ template <typename T> static hipError_t dmalloc(T **p, size_t n)
 }
 
 struct sh_lanes;
+struct EnetState;                        // enet_api.inc
 // what sh_glm_setup was called with: the lanes of the context (lanes_api.inc) are set up from it
 struct GlmSetupArgs { std::vector<double> y, W; int q = 0, continuous = 0, force_firth = 0; double null_llf = 0, null_firth = 0, pret = 1, lrtt = 1;
                       std::string route; };   // (route: the SEERHIP_ROUTE string the set-up ran under)
@@ -163,6 +172,8 @@ struct sh_ctx {
     // ---- staging for the host-pointer entry points
     int64_t cap_bits = 0, cap_out = 0, cap_flags = 0;
     uint8_t *d_bits = nullptr; double *d_out = nullptr; uint32_t *d_flags = nullptr;
+    // ---- the whole-genome elastic net's resident bit matrix and last fit (sh_enet_*)
+    EnetState *enet = nullptr;
 };
 
 // ---- small device -> host read-backs (list lengths, counts) WITHOUT the copy engine ------------------------------------------------------------
@@ -184,6 +195,7 @@ static int ensure_rb(sh_ctx *c);
 static int readback_sync(sh_ctx *c, hipStream_t st, const int *a, const int *b, const int *c2, const int *d, int *dst);
 
 static void lanes_destroy(sh_ctx *c);
+static void enet_free(sh_ctx *c);
 static int lanes_wait(sh_ctx *c);
 static void lanes_set_timing(sh_ctx *c, int on);
 static int lanes_add_timing(sh_ctx *c, double *total_ms, int64_t *launches);
@@ -548,6 +560,7 @@ void sh_destroy(sh_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     lanes_destroy(c);
+    enet_free(c);
     free_ws(c);
     if (c->h_nkeep) hipHostFree(c->h_nkeep);
     if (c->h_rb) hipHostFree(c->h_rb);
@@ -1123,5 +1136,6 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "job_api.inc"
 #include "job_run.inc"
 #include "vcf_api.inc"
+#include "enet_api.inc"
 
 }  // extern "C"

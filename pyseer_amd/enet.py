@@ -1,0 +1,360 @@
+"""Whole-genome elastic net (pyseer/enet.py) on the device: a resident bit matrix, its phenotype correlations, and the
+cross-validated elastic-net path (sh_enet_*, include/seerhip.h).  The host parts that carry no weight -- fold assignment,
+sample weights, the quantile cut -- are here in numpy."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from .packing import row_bytes_for
+
+GAUSSIAN, BINOMIAL = 0, 1
+
+
+def assign_folds(n_samples, n_folds, seed=1):
+    """Balanced random folds as cvglmnet draws them (sample i of a random order goes to fold i mod F), from a seeded
+    generator (--enet-seed): glmnet_python's own draw is unseeded and cannot be reproduced."""
+    if n_folds < 2 or n_folds > n_samples:
+        raise ValueError("n_folds must lie in [2, n_samples]")
+    perm = np.random.default_rng(seed).permutation(n_samples)
+    fold = np.empty(n_samples, dtype=np.int32)
+    fold[perm] = np.arange(n_samples, dtype=np.int32) % n_folds
+    return fold
+
+
+def sequence_weights(cluster_ids):
+    """pyseer/__main__.py:650-654: every sample weighs 1 / (size of its lineage cluster)."""
+    cluster_ids = np.asarray(cluster_ids)
+    _, inv, counts = np.unique(cluster_ids, return_inverse=True, return_counts=True)
+    return 1.0 / counts[inv].astype(float)
+
+
+def correlation_cut(abs_cor, quantile):
+    """enet.py:420: indices whose |correlation| is strictly above numpy's (linear-interpolation) percentile of ALL values;
+    NaN rows (no carriers) never pass and, as in the reference, one NaN makes the percentile NaN and nothing passes."""
+    abs_cor = np.asarray(abs_cor, dtype=float)
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(abs_cor > np.percentile(abs_cor, quantile * 100))[0]
+
+
+class EnetFit(object):
+    """Result of EnetMatrix.fit: arrays over the fitted part of the path."""
+
+    def __init__(self, owner, out, arrays, n_cov):
+        n = out.n_lambda
+        self._owner = owner
+        self.n_lambda, self.i_min, self.n_cov = n, out.i_min, n_cov
+        self.lambdas = arrays["lambda_"][:n].copy()
+        self.cvm, self.cvsd = arrays["cvm"][:n].copy(), arrays["cvsd"][:n].copy()
+        self.dev_ratio, self.nzero = arrays["dev_ratio"][:n].copy(), arrays["nzero"][:n].copy()
+        self.fold_dev = arrays["fold_dev"][:, :n].copy()
+        self.fold_weight = arrays["fold_weight"].copy()
+        self.beta0, self.beta = out.beta0, arrays["beta"]
+        self.kkt_rounds, self.cd_sweeps, self.cd_steps, self.state_in_lds = out.kkt_rounds, out.cd_sweeps, out.cd_steps, bool(out.state_in_lds)
+
+    def betas_at(self, i_lambda, problem=0):
+        """(intercept, slopes[n_cov + rows]) on the original scale: problem 0 = the full fit, 1 + k = fold k held out."""
+        return self._owner._betas_at(problem, i_lambda)
+
+    def eta_at(self, i_lambda):
+        return self._owner._eta_at(i_lambda)
+
+
+class EnetMatrix(object):
+    """The variants of a whole-genome fit, resident on the device of `engine`."""
+
+    def __init__(self, engine, capacity):
+        self._e, self._lib, self._h = engine, engine._lib, engine._h
+        self.n = engine.n
+        self.row_bytes = row_bytes_for(self.n)
+        _abi.check(self._lib.sh_enet_begin(self._h, self.row_bytes, int(capacity)))
+        self._open = True
+
+    def close(self):
+        if self._open and self._e._h:
+            self._lib.sh_enet_end(self._h)
+        self._open = False
+
+    @property
+    def rows(self):
+        return int(self._lib.sh_enet_rows(self._h))
+
+    def _u8(self, a, V):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.shape != (V, self.row_bytes):
+            raise ValueError("packed rows must be (V, %d) bytes" % self.row_bytes)
+        return a
+
+    def append(self, present, missing=None, flip=None):
+        """Add packed rows; flip[v]: store row v by its absences (af > 0.5), a missing call being 0 (enet.py:95-106)."""
+        present = np.ascontiguousarray(present, dtype=np.uint8)
+        V = present.shape[0]
+        present = self._u8(present, V)
+        missing = None if missing is None else self._u8(missing, V)
+        flip = None if flip is None else np.ascontiguousarray(flip, dtype=np.uint8)
+        if flip is not None and flip.shape != (V,):
+            raise ValueError("flip must have one entry per row")
+        p8 = lambda a: None if a is None else a.ctypes.data_as(_abi.c_u8p)
+        _abi.check(self._lib.sh_enet_append(self._h, p8(present), p8(missing), p8(flip), V))
+
+    def correlations(self, y):
+        if self.rows < 1:
+            raise ValueError("No variants passed filters")
+        y = np.ascontiguousarray(y, dtype=float)
+        out = np.empty(self.rows)
+        _abi.check(self._lib.sh_enet_correlations(self._h, y.ctypes.data_as(_abi.c_dp), out.ctypes.data_as(_abi.c_dp)))
+        return out
+
+    def carrier_sums(self, vectors):
+        """(n_vectors, N) -> (n_vectors, rows): sum of each vector over the carriers of every row (k_enet_grad)."""
+        v = np.ascontiguousarray(np.asarray(vectors, dtype=float).reshape(-1, self.n))
+        out = np.empty((v.shape[0], self.rows))
+        _abi.check(self._lib.sh_enet_carrier_sums(self._h, v.ctypes.data_as(_abi.c_dp), v.shape[0], out.ctypes.data_as(_abi.c_dp)))
+        return out
+
+    def keep(self, idx):
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        _abi.check(self._lib.sh_enet_keep(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size))
+
+    def get_rows(self, idx):
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        out = np.zeros((idx.size, self.row_bytes), dtype=np.uint8)
+        _abi.check(self._lib.sh_enet_get_rows(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, out.ctypes.data_as(_abi.c_u8p)))
+        return out
+
+    def fit(self, y, continuous, alpha, weights=None, covariates=None, fold_id=None, n_folds=0, thresh=1e-7, n_lambda=100,
+            lambda_min_ratio=0.0, state_in_global=False, lambdas=None):
+        """Cross-validated elastic-net path.  covariates: (N, n_cov) or None; fold_id: (N,) ints in [0, n_folds)."""
+        if self.rows < 1:
+            raise ValueError("No variants passed filters")
+        if not (0.0 <= alpha <= 1.0):
+            raise ValueError("alpha must lie in [0, 1]")
+        N, P = self.n, self.rows
+        y = np.ascontiguousarray(y, dtype=float)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=float)
+        cov = None
+        n_cov = 0
+        if covariates is not None and np.size(covariates):
+            cov = np.ascontiguousarray(np.asarray(covariates, dtype=float).reshape(N, -1).T)     # one column after the other
+            n_cov = cov.shape[0]
+        fid = None if fold_id is None else np.ascontiguousarray(fold_id, dtype=np.int32)
+        if fid is not None and not n_folds:
+            n_folds = int(fid.max()) + 1
+        seq = None
+        if lambdas is not None:
+            seq = np.ascontiguousarray(lambdas, dtype=float)
+            n_lambda = seq.size
+        opts = _abi.EnetOpts(int(n_lambda), 0, int(bool(state_in_global)), 0, float(thresh), float(lambda_min_ratio),
+                             None if seq is None else seq.ctypes.data_as(_abi.c_dp))
+        arrays = {k: np.full(n_lambda, np.nan) for k in ("lambda_", "cvm", "cvsd", "dev_ratio")}
+        arrays["fold_dev"] = np.full((max(n_folds, 1), n_lambda), np.nan)
+        arrays["fold_weight"] = np.zeros(max(n_folds, 1))
+        arrays["beta"] = np.zeros(n_cov + P)
+        arrays["nzero"] = np.zeros(n_lambda, dtype=np.int32)
+        out = _abi.EnetOut()
+        for k in ("lambda_", "cvm", "cvsd", "dev_ratio", "fold_dev", "fold_weight", "beta"):
+            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_dp))
+        out.nzero = arrays["nzero"].ctypes.data_as(C.POINTER(C.c_int32))
+        dp = lambda a: None if a is None else a.ctypes.data_as(_abi.c_dp)
+        _abi.check(self._lib.sh_enet_fit(self._h, dp(y), dp(w), dp(cov), n_cov, None if fid is None else fid.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         int(n_folds), BINOMIAL if not continuous else GAUSSIAN, float(alpha), C.byref(opts), C.byref(out)))
+        self._n_coef = n_cov + P
+        return EnetFit(self, out, arrays, n_cov)
+
+    def _betas_at(self, problem, i_lambda):
+        b0 = C.c_double()
+        beta = np.zeros(self._n_coef)
+        _abi.check(self._lib.sh_enet_betas_at(self._h, int(problem), int(i_lambda), C.byref(b0), beta.ctypes.data_as(_abi.c_dp)))
+        return b0.value, beta
+
+    def _eta_at(self, i_lambda):
+        eta = np.zeros(self.n)
+        _abi.check(self._lib.sh_enet_eta_at(self._h, int(i_lambda), eta.ctypes.data_as(_abi.c_dp)))
+        return eta
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the command line's --wg enet (pyseer/__main__.py:598-712 over pyseer/enet.py)
+# ---------------------------------------------------------------------------------------------------------------
+TEST_BETAS = None          # test-only hook: a function (n_cov, var_indices) -> betas[1 + n_cov + P] used instead of the fit's
+
+
+def load_all_vars(engine, var_type, p, burden, burden_regions, infile, all_strains, sample_order, min_af, max_af, max_missing, uncompressed):
+    """pyseer/enet.py:33-118 with the matrix on the device: (EnetMatrix, var_indices, number of variants read).  The filters are the
+    reference's strict inequalities; var_indices count every variant read."""
+    from .input import read_variant
+    n, rb = len(p), row_bytes_for(len(p))
+    pres, miss, flip, selected, var_idx = [], [], [], [], 0
+    while True:
+        eof, k, var_name, kstrains, nkstrains, af, missing = read_variant(infile, p, var_type, burden, burden_regions, uncompressed,
+                                                                          all_strains, sample_order)
+        if eof:
+            break
+        if k is not None and af > min_af and af < max_af and missing < max_missing:
+            k = np.asarray(k, dtype=float)
+            pres.append(k == 1)
+            miss.append(np.isnan(k))
+            flip.append(af > 0.5)                                     # enet.py:97: coded by the absences
+            selected.append(var_idx)
+        var_idx += 1
+    if not selected:
+        raise ValueError("No variants passed filters")
+
+    def pack(rows):
+        out = np.zeros((len(rows), rb), dtype=np.uint8)
+        pk = np.packbits(np.array(rows, dtype=bool).reshape(len(rows), n), axis=1, bitorder="little")
+        out[:, :pk.shape[1]] = pk
+        return out
+    M = EnetMatrix(engine, len(selected))
+    for s in range(0, len(selected), 65536):
+        M.append(pack(pres[s:s + 65536]), pack(miss[s:s + 65536]), np.array(flip[s:s + 65536], dtype=np.uint8))
+    return M, selected, var_idx
+
+
+def _r2(y_true, y_pred):
+    """sklearn.metrics.r2_score for one output."""
+    ss_res, ss_tot = np.sum((y_true - y_pred) ** 2), np.sum((y_true - np.mean(y_true)) ** 2)
+    return 1.0 - ss_res / ss_tot
+
+
+def write_lineage_predictions(true_values, predictions, fold_ids, lineage_dict, continuous, out):
+    """pyseer/enet.py:309-376: R2 (and TP / TN / FP / FN for a binary phenotype) within each lineage."""
+    out.write("\t".join(['Lineage', 'Size', 'R2']) + ("" if continuous else "\t" + "\t".join(['TP', 'TN', 'FP', 'FN'])) + "\n")
+    for fold in range(int(max(fold_ids)) + 1):
+        idx = np.where(fold_ids == fold)[0]
+        y_true, y_pred = true_values[idx], predictions[idx].reshape(-1)
+        fold_r2 = np.nan if np.all(y_true == y_true[0]) else _r2(y_true, y_pred)
+        line = [lineage_dict[fold], str(idx.shape[0]), '%.3f' % fold_r2]
+        if not continuous:
+            tp, tn = int(np.sum((y_true == 1) & (y_pred == 1))), int(np.sum((y_true == 0) & (y_pred == 0)))
+            fp, fn = int(np.sum((y_true == 0) & (y_pred == 1))), int(np.sum((y_true == 1) & (y_pred == 0)))
+            line += [str(x) for x in (tp, tn, fp, fn)]
+        out.write("\t".join(line) + "\n")
+
+
+def write_predictions(samples, true_values, predictions, fold_ids, lineage_dict, fname):
+    """pyseer/enet.py:258-306."""
+    with open(fname, 'w') as fout:
+        lin = lineage_dict is not None and fold_ids is not None
+        fout.write("\t".join(["sample"] + (["lineage", "fold_id"] if lin else []) + ["true_value", "predicted_value"]) + "\n")
+        for i, sample in enumerate(samples):
+            mid = [lineage_dict[fold_ids[i]], str(fold_ids[i])] if lin else []
+            fout.write("\t".join([sample] + mid + [str(true_values[i]), str(predictions[i])]) + "\n")
+
+
+def find_enet_selected(enet_betas, var_indices, p, c, var_type, fit_seer, burden, burden_regions, infile, all_strains, sample_order,
+                       continuous, find_lineage, lin, uncompressed):
+    """pyseer/enet.py:424-516: the variants with a non-zero slope, in file order, as Enet tuples."""
+    from .classes import Enet
+    from .input import read_variant
+    from .model import fixed_effects_regression, pre_filtering, fit_lineage_effect
+    enet_betas = enet_betas[c.shape[1] + 1:]
+    current_var = 0
+    for beta, var_idx in zip(enet_betas, var_indices):
+        if beta == 0:
+            continue
+        while current_var < var_idx:
+            read_variant(infile, p, var_type, burden, burden_regions, uncompressed, all_strains, sample_order, noparse=True)
+            current_var += 1
+        eof, k, var_name, kstrains, nkstrains, af, missing = read_variant(infile, p, var_type, burden, burden_regions, uncompressed,
+                                                                          all_strains, sample_order)
+        current_var += 1
+        notes = []
+        if fit_seer is not None:
+            m, null_res, null_firth = fit_seer
+            s = fixed_effects_regression(var_name, p.values, k, m, c, af, None, find_lineage, lin, 1, 1, null_res, null_firth,
+                                         kstrains, nkstrains, continuous)
+            pval, adj_pval, max_lineage, notes = s.prep, s.pvalue, s.max_lineage, s.notes
+        else:
+            pval, bad = pre_filtering(p.values, k, continuous)
+            adj_pval = np.nan
+            if bad:
+                notes.append("bad-chisq")
+            max_lineage = fit_lineage_effect(lin, c, k) if find_lineage else None
+        yield Enet(var_name, af, pval, adj_pval, beta, max_lineage, kstrains, nkstrains, notes)
+
+
+def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_dict, clusters_full, dict_full, enet_seer, out, err):
+    """The --wg enet branch of the command line; returns the closing counters (prefilter, tested, printed)."""
+    import collections
+    from decimal import Decimal
+    from .engine import Engine
+    from .input import open_variant_file
+    from .utils import format_output
+    kmers = list(options.kmers) if options.kmers else []
+    var_type, var_file = ("kmers", kmers[0]) if kmers else (("vcf", options.vcf) if options.vcf else ("Rtab", options.pres))
+    all_strains = set(p.index)
+
+    def reopen():
+        regions = collections.deque([]) if options.burden else None
+        infile, sample_order = open_variant_file(var_type, var_file, options.burden, regions, options.uncompressed)
+        return infile, sample_order, regions
+    err.write("Reading all variants\n")
+    engine = Engine(len(p), device=options.gpu)
+    infile, sample_order, regions = reopen()
+    M, var_indices, loaded = load_all_vars(engine, var_type, p, bool(options.burden), regions, infile, all_strains, sample_order,
+                                           options.min_af, options.max_af, options.max_missing, options.uncompressed)
+    var_indices = np.array(var_indices)
+    pv = p.values.astype(float)
+    if options.cor_filter > 0:
+        err.write("Applying correlation filtering\n")
+        keep = correlation_cut(M.correlations(pv), options.cor_filter)
+        if keep.size == 0:
+            raise ValueError("No variants passed filters")
+        M.keep(keep)
+        var_indices = var_indices[keep]
+    tested = len(var_indices)
+    prefilter = loaded - tested
+    weights, fold_ids = np.ones(len(p)), None
+    if options.sequence_reweighting:                                  # __main__.py:650-654
+        weights = np.matmul(clusters_full, 1 / np.sum(clusters_full, axis=0)).reshape(-1)
+    if options.lineage_clusters:
+        fold_ids = np.where(clusters_full == 1)[1]
+        assert fold_ids.shape[0] == weights.shape[0]
+    err.write("Fitting elastic net to top " + str(tested) + " variants\n")
+    folds = fold_ids if fold_ids is not None else assign_folds(len(p), options.n_folds, options.enet_seed)
+    n_folds = int(folds.max()) + 1
+    cv = cov.values.astype(float) if cov.shape[1] > 0 else None
+    fit = M.fit(pv, options.continuous, options.alpha, weights=weights, covariates=cv, fold_id=folds, n_folds=n_folds,
+                thresh=options.enet_thresh)
+    betas = np.concatenate([[fit.beta0], fit.beta])
+    if TEST_BETAS is not None:
+        betas = np.asarray(TEST_BETAS(cov.shape[1], var_indices), dtype=float)
+    eta = fit.eta_at(fit.i_min)
+    preds = eta if options.continuous else (eta > 0).astype(float)   # cvglmnetPredict: 'link' / 'class'
+    sstot = np.sum(np.square(pv - np.mean(pv)))
+    r2 = (1 - np.sum(np.square(pv - preds)) / sstot) if sstot != 0 else None
+    err.write("Best penalty (lambda) from cross-validation: " + '%.2E' % Decimal(fit.lambdas[fit.i_min]) + "\n")
+    if not options.continuous:
+        err.write("Best model deviance from cross-validation: " + '%.3f' % Decimal(fit.cvm[fit.i_min]) + " ± " +
+                  '%.2E' % Decimal(fit.cvsd[fit.i_min]) + "\n")
+    err.write("Best R^2 from cross-validation: " + ('%.3f' % Decimal(float(r2)) if r2 is not None else "nan") + "\n")
+    if fold_ids is not None:
+        err.write("Predictions within each lineage\n")
+        write_lineage_predictions(pv, preds, fold_ids, dict_full, options.continuous, err)
+    if options.save_predictions is not None:
+        err.write("Writing predictions to " + options.save_predictions + "\n")
+        write_predictions(list(p.index), p.values, preds, fold_ids, dict_full if fold_ids is not None else None, options.save_predictions)
+    err.write("Finding and printing selected variants\n")
+    for beta, covariate in zip(betas[1:cov.shape[1] + 1], cov.columns):
+        if beta != 0:
+            err.write("Kept covariate '" + str(covariate) + "', slope: " + '%.2E' % Decimal(float(beta)) + "\n")
+    header = ['variant', 'af', 'filter-pvalue', 'lrt-pvalue', 'beta']
+    lineage_col = bool(options.lineage or (options.sequence_reweighting and options.lineage_clusters))
+    if lineage_col:
+        header.append('lineage')
+    if options.print_samples:
+        header += ['k-samples', 'nk-samples']
+    header.append('notes')
+    out.write('\t'.join(header) + "\n")
+    M.close()
+    engine.close()
+    infile, sample_order, regions = reopen()
+    printed = 0
+    label = (lineage_dict if lineage_dict is not None else []) if lineage_col else None
+    for x in find_enet_selected(betas, var_indices, p, cov, var_type, (m, null_fit, firth_null) if enet_seer else None, bool(options.burden),
+                                regions, infile, all_strains, sample_order, options.continuous, bool(options.lineage), lineage_clusters,
+                                options.uncompressed):
+        printed += 1
+        out.write(format_output(x, label, 'enet', options.print_samples) + "\n")
+    return prefilter, tested, printed
