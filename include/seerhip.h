@@ -368,6 +368,14 @@ int         sh_burden_fold(sh_ctx *ctx, const uint8_t *present, const uint8_t *m
  * fit and each cross-validation fold are that matrix with other sample weights (a held-out sample has weight 0).
  *   begin / append / end: reserve `capacity` rows of row_bytes (layout of sh_lmm_batch), add V rows.  flip[v] != 0 (may be NULL) stores the
  *     row in the minor-allele coding of enet.py:95-106: by its absences, a missing call (the `missing` rows, may be NULL) being 0 either way.
+ *   ingest: load_all_vars' loop (enet.py:33-118) for a block of V parsed rows WITHOUT missing calls (k-mers: the native reader's or the packed
+ *     cache's raw blocks, every parsed line, host pointer), decided on the device (k_enet_ingest_*): a row is kept iff its carriers over the
+ *     first n_samples bits (padding bits are not trusted) lie in [min_count, max_count] -- the caller derives the two from the reference's
+ *     strict `af > min_af and af < max_af` evaluated at every count; an empty interval keeps nothing -- and is stored after the rows already
+ *     there, in the order of the block, by its absences when 2 * carriers > n_samples (enet.py:95-106).  Returns the number of rows kept
+ *     (their index in the block and their carrier count in kept_idx / kept_count, V entries each, the caller's) or a negative status.
+ *     The matrix grows as needed (sh_enet_begin's capacity is the initial one: at least twice the rows, copied device to device); a growth
+ *     that fails returns SH_ENOMEM with the matrix as it was.  Forgets the last fit, like append.
  *   correlations: |cor(row, y)| of enet.py:398-418 for every row, NaN for a row without carriers.  The quantile cut is the caller's.
  *   keep: compact the matrix to rows idx[0 .. n_keep) (ascending or not); get_rows: copy rows idx[] out (host pointer), e.g. the selected
  *     variants for the per-variant engine, so that no input is read twice (enet.py:424 find_enet_selected reads it again).
@@ -400,6 +408,7 @@ typedef struct sh_enet_out {
 } sh_enet_out;
 int     sh_enet_begin(sh_ctx *ctx, int64_t row_bytes, int64_t capacity);
 int     sh_enet_append(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, const uint8_t *flip, int64_t V);
+int64_t sh_enet_ingest(sh_ctx *ctx, const uint8_t *bits, int64_t V, int32_t min_count, int32_t max_count, int32_t *kept_idx, int32_t *kept_count);
 int64_t sh_enet_rows(sh_ctx *ctx);
 int     sh_enet_correlations(sh_ctx *ctx, const double *y, double *out_abs_cor);
 /* out[f * rows + j] = sum over the carriers i of row j of vectors[f * n_samples + i] (k_enet_grad, 16 vectors a pass): the pass behind the

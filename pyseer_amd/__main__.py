@@ -85,7 +85,7 @@ import pandas as pd
 
 from . import __version__
 from .classes import Seer, LMM, FLAG_FILTER, FLAG_PREFILTER, notes_from_flags
-from .input import (check_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
+from .input import (check_kmers_gzipped, check_packed_cache, plan_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
                     iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_native_multi, iter_packed_blocks_cached,
                     iter_packed_blocks_vcf_native, load_burden,
                     PackedCacheWriter, packed_cache_complete)
@@ -216,8 +216,14 @@ def main(argv=None):
                 _die('%s writes pickles of reference-internal objects and is not built in pyseer_amd\n' % name_)
         if options.gpus is not None or options.packed_part:
             _die('--wg enet runs on one device: --gpus and --packed-part are not available with it\n')
-        if options.load_packed or options.save_packed or options.packed_cache or (options.kmers and len(options.kmers) > 1):
+        if (options.load_packed or options.save_packed or options.packed_cache or (options.kmers and len(options.kmers) > 1)) and \
+                (options.python_reader or options.pres or not (options.kmers or options.load_packed)):
+            # (raw blocks and the cache hold k-mer lines, which have no missing calls: --pres, --vcf and --python-reader keep the line-by-line path)
             _die('--wg enet reads one variant file through the Python readers: the packed cache and several --kmers files are not available with it\n')
+        if options.load_packed and options.save_packed and os.path.realpath(options.load_packed) == os.path.realpath(options.save_packed):
+            _die('--save-packed and --load-packed name the same file\n')
+        if options.kmers and len(options.kmers) > 1 and (options.load_packed or options.save_packed or options.packed_cache):
+            _die('Several --kmers files need the native reader and cannot be combined with a packed cache\n')
         if not (0.0 <= options.alpha <= 1.0):
             _die('--alpha must lie in [0, 1]\n')
     if options.max_dimensions < 1:
@@ -430,11 +436,7 @@ def main(argv=None):
         for e_ in engs:
             e_.set_af_filter(options.min_af, options.max_af)
     if native and not options.uncompressed and not options.load_packed:
-        for vf in (kmer_files or [var_file]):
-            with open(vf, "rb") as fh:                     # the reference's gzip.open raises on plain text (input.py:271-276)
-                if fh.read(2) != b"\x1f\x8b":
-                    sys.stderr.write("Not a gzipped file (%s): use --uncompressed for plain-text k-mers\n" % vf)
-                    sys.exit(1)
+        check_kmers_gzipped(kmer_files or [var_file])
     if native_vcf:
         if options.burden:
             load_burden(options.burden, burden_regions)
@@ -464,38 +466,7 @@ def main(argv=None):
 
     cache_out, cache_stamp = None, None
     if options.packed_cache and native and not options.load_packed and not options.save_packed:
-        # the automatic form of --save-packed / --load-packed: one file next to the input, tied to it by size + mtime (a sidecar stamp),
-        # and to the run by the sample list the cache itself stores
-        import os as _os
-        side = var_file + ".seerpack"
-        st = _os.stat(var_file)
-        stamp = "%d %d" % (st.st_size, int(st.st_mtime))
-        fresh = False
-        try:
-            fresh = _os.path.exists(side) and open(side + ".stamp").read().strip() == stamp
-        except (IOError, OSError):
-            fresh = False
-        if fresh and not packed_cache_complete(side):
-            sys.stderr.write("Packed cache %s is incomplete (an interrupted run); parsing %s again\n" % (side, var_file))
-            fresh = False
-        if fresh:
-            try:
-                next(iter(iter_packed_blocks_cached(p, side, options.min_af, options.max_af, 1)), None)    # header + sample list check
-                options.load_packed = side
-            except ValueError:
-                sys.stderr.write("Packed cache %s was written for other samples; parsing %s again\n" % (side, var_file))
-                fresh = False
-            except IOError as ex:
-                sys.stderr.write("Packed cache %s cannot be used (%s); parsing %s again\n" % (side, ex, var_file))
-                fresh = False
-        if not fresh:
-            # the cache is written to a temporary name and renamed when the run has read the whole input; the stamp follows the rename
-            # (PackedCacheWriter.close), so an interrupted run leaves neither
-            if _os.access(_os.path.dirname(_os.path.abspath(side)) or ".", _os.W_OK):
-                options.save_packed = side
-                cache_stamp = (side + ".stamp", stamp)
-            else:
-                sys.stderr.write("Cannot write a packed cache next to %s; continuing without\n" % var_file)
+        cache_stamp = plan_packed_cache(options, p, var_file)
     # ---- the job stream (round 5; include/seerhip.h sh_job_*): unless a cross-check sink is asked for (round 6: --lineage, --output-patterns and --print-samples
     # run inside the stream too: sh_job_set_lineage / _patterns / _samples) a block goes to the library as parsed and comes back as the text of its printed rows: the AF
     # window, the NaN masks, the counters and the choice of rows run on the device, the host formats printed rows only.  Output without

@@ -6,6 +6,8 @@ struct EnetPoint { double b0 = 0.0; std::vector<int> idx; std::vector<double> va
 struct EnetState {
     int64_t NW = 0, cap = 0, P = 0;
     uint64_t *d_B = nullptr;
+    // sh_enet_ingest: the block as it came from the host, and per row its count and destination, the kept rows' indices and counts, the total
+    uint64_t *d_stage = nullptr; int32_t *d_meta = nullptr; int64_t stage_rows = 0;
     // the last fit
     int F1 = 0, n_cov = 0, n_lam = 0, N = 0;
     std::vector<std::vector<EnetPoint>> path;                        // [problem][lambda]
@@ -23,9 +25,13 @@ struct DevBuf {                                                      // a device
 // the solutions of the last fit belong to the matrix they were fitted on: a changed matrix, or a fit that fails, leaves none
 static void enet_forget_fit(EnetState *e) { e->n_lam = 0; e->F1 = 0; e->path.clear(); e->eta.clear(); }
 
+// (the staging of the last ingested block is of no use to a fit or a cut: up to 166 MB at N = 5000 go back to the device)
+static void enet_free_stage(EnetState *e) { hipFree(e->d_stage); hipFree(e->d_meta); e->d_stage = nullptr; e->d_meta = nullptr; e->stage_rows = 0; }
+
 static void enet_free(sh_ctx *c)
 {
     if (!c->enet) return;
+    enet_free_stage(c->enet);
     hipFree(c->enet->d_B);
     delete c->enet; c->enet = nullptr;
 }
@@ -67,6 +73,60 @@ int sh_enet_append(sh_ctx *c, const uint8_t *present, const uint8_t *missing, co
     return SH_OK;
 }
 
+// room for `rows` rows: a new allocation of at least twice the capacity, the stored rows copied device to device; a failure leaves the matrix as it was
+static int enet_reserve(sh_ctx *c, int64_t rows)
+{
+    EnetState *e = c->enet;
+    if (rows <= e->cap) return SH_OK;
+    uint64_t *nb = nullptr;
+    int64_t cap = std::max<int64_t>(rows, 2 * e->cap);
+    if (hipMalloc((void **)&nb, (size_t)cap * e->NW * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        cap = rows; nb = nullptr;                                     // (twice does not fit: what is needed now may)
+        if (hipMalloc((void **)&nb, (size_t)cap * e->NW * 8) != hipSuccess) { (void)hipGetLastError(); return fail(SH_ENOMEM, "sh_enet_ingest: the bit matrix does not fit the device"); }
+    }
+    if (e->P > 0) {
+        const hipError_t rc = hipMemcpy(nb, e->d_B, (size_t)e->P * e->NW * 8, hipMemcpyDeviceToDevice);
+        if (rc != hipSuccess) { hipFree(nb); return fail(SH_EHIP, std::string("sh_enet_ingest: copy of the stored rows: ") + hipGetErrorString(rc)); }
+    }
+    hipFree(e->d_B); e->d_B = nb; e->cap = cap;
+    return SH_OK;
+}
+
+int64_t sh_enet_ingest(sh_ctx *c, const uint8_t *bits, int64_t V, int32_t min_count, int32_t max_count, int32_t *kept_idx, int32_t *kept_count)
+{
+    if (!c || !c->enet) return fail(SH_EINVAL, "sh_enet_ingest before sh_enet_begin");
+    EnetState *e = c->enet;
+    if (V < 0 || V > INT32_MAX) return fail(SH_ESHAPE, "sh_enet_ingest: a block holds 0 .. 2^31 - 1 rows");
+    if (V > 0 && (!bits || !kept_idx || !kept_count)) return fail(SH_EINVAL, "sh_enet_ingest: null argument");
+    enet_forget_fit(e);
+    if (V == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (V > e->stage_rows) {
+        enet_free_stage(e);
+        if (hipMalloc((void **)&e->d_stage, (size_t)V * e->NW * 8) != hipSuccess || hipMalloc((void **)&e->d_meta, ((size_t)4 * V + 1) * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError(); enet_free_stage(e);
+            return fail(SH_ENOMEM, "sh_enet_ingest: the block does not fit the device");
+        }
+        e->stage_rows = V;
+    }
+    int32_t *d_cnt = e->d_meta, *d_dest = d_cnt + V, *d_kidx = d_dest + V, *d_kcnt = d_kidx + V, *d_n = d_kcnt + V;
+    HIPCHK(hipMemcpyAsync(e->d_stage, bits, (size_t)V * e->NW * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(shk_enet_ingest_count(c->stream, e->d_stage, V, (int)e->NW, c->N, min_count, max_count, d_cnt, d_dest, d_kidx, d_kcnt, d_n));
+    int32_t kept = 0;
+    HIPCHK(hipMemcpyAsync(&kept, d_n, sizeof(kept), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (kept < 0 || kept > V) return fail(SH_EHIP, "sh_enet_ingest: the scan returned an impossible count");
+    if (kept == 0) return 0;
+    const int rc = enet_reserve(c, e->P + kept); if (rc) return rc;
+    HIPCHK(shk_enet_ingest_scatter(c->stream, e->d_stage, V, (int)e->NW, c->N, d_cnt, d_dest, e->d_B + e->P * e->NW));
+    HIPCHK(hipMemcpyAsync(kept_idx, d_kidx, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(kept_count, d_kcnt, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    e->P += kept;
+    return kept;
+}
+
 int sh_enet_correlations(sh_ctx *c, const double *y, double *out_abs_cor)
 {
     if (!c || !c->enet) return fail(SH_EINVAL, "sh_enet_correlations before sh_enet_begin");
@@ -98,6 +158,7 @@ int sh_enet_keep(sh_ctx *c, const int64_t *idx, int64_t n_keep)
     EnetState *e = c->enet;
     if (n_keep < 0 || n_keep > e->P) return fail(SH_ESHAPE, "sh_enet_keep: bad count");
     HIPCHK(hipSetDevice(c->device));
+    enet_free_stage(e);
     uint64_t *nb = nullptr;
     HIPCHK(hipMalloc((void **)&nb, (size_t)std::max<int64_t>(n_keep, 1) * e->NW * 8));
     const int rc = enet_gather(c, idx, n_keep, nb);
@@ -163,6 +224,7 @@ int sh_enet_fit(sh_ctx *c, const double *y, const double *weights, const double 
     const int max_sweeps = opts->max_sweeps > 0 ? opts->max_sweeps : 100000;
     const int F1 = n_folds + 1;
     HIPCHK(hipSetDevice(c->device));
+    enet_free_stage(e);
     if (family == 1) for (int i = 0; i < N; ++i) if (y[i] != 0.0 && y[i] != 1.0) return fail(SH_EINVAL, "sh_enet_fit: a binomial response is 0 or 1");
     for (int i = 0; i < N && n_folds; ++i) if (fold_id[i] < 0 || fold_id[i] >= n_folds) return fail(SH_EINVAL, "sh_enet_fit: fold_id outside [0, n_folds)");
 

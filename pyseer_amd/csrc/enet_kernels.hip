@@ -3,6 +3,7 @@
 // One bit matrix B (P rows of row_bytes, LSB first, bits at and above N are 0) stays on the device; the full fit and every cross-validation
 // fold are the SAME problem with different sample weights (a held-out sample has weight 0), so they share B and differ in N-vectors only.
 //   k_enet_store        minor-allele coding of load_all_vars (enet.py:95-106) while the rows are put in place
+//   k_enet_ingest_*     the same rule and coding applied ON the device to a block of parsed k-mer rows: count, ordered scan, compacted store
 //   k_enet_moments      |correlation| of every row with the phenotype (enet.py:379-421)
 //   k_enet_grad         G[f][j] = sum over the carriers i of row j of V[f][i], up to 16 vectors per pass, fp64: weighted means, training
 //                       counts, lambda_max, the strong rule and the KKT check over ALL rows
@@ -65,6 +66,74 @@ __global__ void k_enet_gather(const uint64_t *__restrict__ src, const int64_t *_
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * NW) return;
     dst[t] = src[idx[t / NW] * NW + (t % NW)];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// k_enet_ingest_*: a block of V parsed rows (no missing calls: k-mers) goes into B by load_all_vars' rule (enet.py:33-118) without the host
+// looking at a row: count the carriers, keep the rows whose count lies in [lo, hi], give every kept row the number of kept rows before it
+// (the order of the stream is the order of the matrix: no atomics), store it by its minor allele (enet.py:95-106).
+__device__ __forceinline__ uint64_t enet_valid_bits(int wd, int N)
+{
+    const int left = N - wd * 64;
+    return left >= 64 ? ~0ull : left <= 0 ? 0ull : ((1ull << left) - 1ull);
+}
+
+// one wavefront per row: carriers over the first N bits (whatever the reader left in the padding is not counted)
+__global__ void k_enet_ingest_count(const uint64_t *__restrict__ rows, int64_t V, int NW, int N, int32_t *__restrict__ cnt)
+{
+    const int64_t v = (int64_t)blockIdx.x * ENET_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= V) return;
+    const uint64_t *row = rows + v * NW;
+    int c = 0;
+    for (int wd = lane; wd < NW; wd += 64) c += __popcll(row[wd] & enet_valid_bits(wd, N));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if (lane == 0) cnt[v] = c;
+}
+
+// ONE workgroup walks the V counts, ENET_SCAN_TPB at a time: a ballot orders the rows of a wavefront, the LDS the wavefronts of a step, a
+// running total the steps.  dest[v] = position among the kept rows or -1; kept_idx / kept_cnt = block index and carriers of every kept row.
+#define ENET_SCAN_TPB 1024
+__global__ __launch_bounds__(ENET_SCAN_TPB) void k_enet_ingest_scan(const int32_t *__restrict__ cnt, int64_t V, int lo, int hi, int32_t *__restrict__ dest,
+                                                                    int32_t *__restrict__ kept_idx, int32_t *__restrict__ kept_cnt, int32_t *__restrict__ n_kept)
+{
+    __shared__ int wsum[ENET_SCAN_TPB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < V; base += ENET_SCAN_TPB) {
+        const int64_t v = base + tid;
+        const int c = v < V ? cnt[v] : 0;
+        const bool keep = v < V && c >= lo && c <= hi;
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) wsum[wv] = __popcll(b);
+        __syncthreads();
+        int before = __popcll(b & ((1ull << lane) - 1ull)), total = 0;
+        for (int w = 0; w < ENET_SCAN_TPB / 64; ++w) { const int s = wsum[w]; if (w < wv) before += s; total += s; }
+        if (v < V) {
+            dest[v] = keep ? carry + before : -1;
+            if (keep) { kept_idx[carry + before] = (int32_t)v; kept_cnt[carry + before] = c; }
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) *n_kept = carry;
+}
+
+// one wavefront per row: a kept row goes to dst + dest[v] * NW, complemented over the first N bits when more than half the samples carry it
+// (af > 0.5 is 2c > N; exactly N / 2 carriers is not flipped), padding bits 0: the words k_enet_store writes for (present, NULL, flip)
+__global__ void k_enet_ingest_scatter(const uint64_t *__restrict__ rows, int64_t V, int NW, int N, const int32_t *__restrict__ cnt,
+                                      const int32_t *__restrict__ dest, uint64_t *__restrict__ dst)
+{
+    const int64_t v = (int64_t)blockIdx.x * ENET_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= V) return;
+    const int d = dest[v];
+    if (d < 0) return;
+    const bool flip = 2 * (int64_t)cnt[v] > (int64_t)N;
+    const uint64_t *row = rows + v * NW;
+    uint64_t *out = dst + (int64_t)d * NW;
+    for (int wd = lane; wd < NW; wd += 64) { const uint64_t b = row[wd]; out[wd] = (flip ? ~b : b) & enet_valid_bits(wd, N); }
 }
 
 // one wavefront per row: carrier count and carrier sum of yc = y - mean(y);  cor = |ab / sqrt(sum a^2 sum b^2)| with a = k - mean(k)
@@ -307,6 +376,21 @@ hipError_t shk_enet_gather(hipStream_t st, const uint64_t *src, const int64_t *i
     if (n <= 0) return hipSuccess;
     const int64_t t = n * NW;
     hipLaunchKernelGGL(k_enet_gather, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, src, idx, n, NW, dst);
+    return hipGetLastError();
+}
+// count + scan of a block (n_kept is on the device: the caller reads it before it makes room and calls shk_enet_ingest_scatter)
+hipError_t shk_enet_ingest_count(hipStream_t st, const uint64_t *rows, int64_t V, int NW, int N, int lo, int hi, int32_t *cnt, int32_t *dest,
+                                 int32_t *kept_idx, int32_t *kept_cnt, int32_t *n_kept)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_enet_ingest_count, dim3((unsigned)((V + ENET_WAVES - 1) / ENET_WAVES)), dim3(ENET_TPB), 0, st, rows, V, NW, N, cnt);
+    hipLaunchKernelGGL(k_enet_ingest_scan, dim3(1), dim3(ENET_SCAN_TPB), 0, st, cnt, V, lo, hi, dest, kept_idx, kept_cnt, n_kept);
+    return hipGetLastError();
+}
+hipError_t shk_enet_ingest_scatter(hipStream_t st, const uint64_t *rows, int64_t V, int NW, int N, const int32_t *cnt, const int32_t *dest, uint64_t *dst)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_enet_ingest_scatter, dim3((unsigned)((V + ENET_WAVES - 1) / ENET_WAVES)), dim3(ENET_TPB), 0, st, rows, V, NW, N, cnt, dest, dst);
     return hipGetLastError();
 }
 hipError_t shk_enet_moments(hipStream_t st, const uint64_t *B, int64_t P, int NW, int N, const double *yc, double sum_b2, double *out)

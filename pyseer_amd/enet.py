@@ -97,6 +97,22 @@ class EnetMatrix(object):
         p8 = lambda a: None if a is None else a.ctypes.data_as(_abi.c_u8p)
         _abi.check(self._lib.sh_enet_append(self._h, p8(present), p8(missing), p8(flip), V))
 
+    def ingest(self, bits, min_count, max_count):
+        """A block of parsed rows without missing calls (a RawBlock's bits): the rows with min_count <= carriers <= max_count are appended in
+        their order, coded by the minor allele, on the device (k_enet_ingest_*); the matrix grows as needed.  Returns (index in the block,
+        carrier count) of the kept rows."""
+        bits = np.asarray(bits)
+        V = bits.shape[0]
+        if bits.dtype != np.uint8 or bits.shape != (V, self.row_bytes) or not bits.flags.c_contiguous:
+            bits = self._u8(bits, V)
+        idx, cnt = np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        kept = self._lib.sh_enet_ingest(self._h, C.cast(bits.ctypes.data, _abi.c_u8p), V, int(min_count), int(max_count), idx.ctypes.data_as(i32),
+                                        cnt.ctypes.data_as(i32))
+        if kept < 0:
+            _abi.check(int(kept))
+        return idx[:kept], cnt[:kept]
+
     def correlations(self, y):
         if self.rows < 1:
             raise ValueError("No variants passed filters")
@@ -211,6 +227,54 @@ def load_all_vars(engine, var_type, p, burden, burden_regions, infile, all_strai
     return M, selected, var_idx
 
 
+def count_bounds(n, min_af, max_af, max_missing):
+    """load_all_vars' rule for a line without missing calls as an interval of carrier counts: the reference's own expression (enet.py:95)
+    evaluated at every count 0 .. n -- it is monotone in the count, so the kept counts are one interval.  (1, 0) keeps nothing."""
+    af = np.array([float(c) / n for c in range(n + 1)])
+    keep = np.nonzero((af > min_af) & (af < max_af) & (0.0 < max_missing))[0]
+    return (int(keep[0]), int(keep[-1])) if keep.size else (1, 0)
+
+
+def _take_names(blob, off, idx):
+    """(blob, offsets) of the names idx[] of (blob, off), in the order of idx."""
+    blob = np.frombuffer(blob, dtype=np.uint8)
+    off = np.asarray(off, dtype=np.int64)
+    idx = np.asarray(idx, dtype=np.int64)
+    start, length = off[idx], off[idx + 1] - off[idx]
+    new_off = np.zeros(idx.size + 1, dtype=np.int64)
+    np.cumsum(length, out=new_off[1:])
+    src = np.repeat(start - new_off[:-1], length) + np.arange(new_off[-1], dtype=np.int64)
+    return blob[src], new_off
+
+
+def load_all_vars_blocks(engine, p, blocks, min_af, max_af, max_missing, capacity=1 << 16):
+    """load_all_vars for k-mers over the raw block stream of the native reader or the packed cache (input.RawBlock: every parsed line, in
+    order): each block goes to the device as parsed and sh_enet_ingest keeps, codes and appends its rows there.
+    Returns (EnetMatrix, var_indices, number of lines read, names blob, name offsets, carrier counts), the last four per row of the matrix."""
+    n = len(p)
+    lo, hi = count_bounds(n, min_af, max_af, max_missing)
+    M = EnetMatrix(engine, capacity)                                  # (the initial capacity: the matrix grows with the stream)
+    var_idx, blobs, lens, counts, loaded = [], [], [], [], 0
+    try:
+        for blk in blocks:
+            idx, cnt = M.ingest(blk.bits, lo, hi)
+            if idx.size:
+                b, o = _take_names(blk.blob, blk.off, idx)
+                var_idx.append(idx.astype(np.int64) + loaded); blobs.append(b); lens.append(np.diff(o)); counts.append(cnt)
+            loaded += len(blk)
+            if blk.release is not None:
+                blk.release()
+    except BaseException:
+        M.close()
+        raise
+    if not var_idx:
+        M.close()
+        raise ValueError("No variants passed filters")
+    off = np.zeros(sum(x.size for x in lens) + 1, dtype=np.int64)
+    np.cumsum(np.concatenate(lens), out=off[1:])
+    return M, np.concatenate(var_idx), loaded, np.concatenate(blobs), off, np.concatenate(counts)
+
+
 def _r2(y_true, y_pred):
     """sklearn.metrics.r2_score for one output."""
     ss_res, ss_tot = np.sum((y_true - y_pred) ** 2), np.sum((y_true - np.mean(y_true)) ** 2)
@@ -259,19 +323,50 @@ def find_enet_selected(enet_betas, var_indices, p, c, var_type, fit_seer, burden
         eof, k, var_name, kstrains, nkstrains, af, missing = read_variant(infile, p, var_type, burden, burden_regions, uncompressed,
                                                                           all_strains, sample_order)
         current_var += 1
-        notes = []
-        if fit_seer is not None:
-            m, null_res, null_firth = fit_seer
-            s = fixed_effects_regression(var_name, p.values, k, m, c, af, None, find_lineage, lin, 1, 1, null_res, null_firth,
-                                         kstrains, nkstrains, continuous)
-            pval, adj_pval, max_lineage, notes = s.prep, s.pvalue, s.max_lineage, s.notes
-        else:
-            pval, bad = pre_filtering(p.values, k, continuous)
-            adj_pval = np.nan
-            if bad:
-                notes.append("bad-chisq")
-            max_lineage = fit_lineage_effect(lin, c, k) if find_lineage else None
-        yield Enet(var_name, af, pval, adj_pval, beta, max_lineage, kstrains, nkstrains, notes)
+        yield _enet_row(var_name, k, af, kstrains, nkstrains, beta, p, c, fit_seer, continuous, find_lineage, lin)
+
+
+def _enet_row(var_name, k, af, kstrains, nkstrains, beta, p, c, fit_seer, continuous, find_lineage, lin):
+    """the tail of find_enet_selected's loop (pyseer/enet.py:424-516): the Enet tuple of one selected variant."""
+    from .classes import Enet
+    from .model import fixed_effects_regression, pre_filtering, fit_lineage_effect
+    notes = []
+    if fit_seer is not None:
+        m, null_res, null_firth = fit_seer
+        s = fixed_effects_regression(var_name, p.values, k, m, c, af, None, find_lineage, lin, 1, 1, null_res, null_firth,
+                                     kstrains, nkstrains, continuous)
+        pval, adj_pval, max_lineage, notes = s.prep, s.pvalue, s.max_lineage, s.notes
+    else:
+        pval, bad = pre_filtering(p.values, k, continuous)
+        adj_pval = np.nan
+        if bad:
+            notes.append("bad-chisq")
+        max_lineage = fit_lineage_effect(lin, c, k) if find_lineage else None
+    return Enet(var_name, af, pval, adj_pval, beta, max_lineage, kstrains, nkstrains, notes)
+
+
+def selected_from_rows(enet_betas, rows, names, counts, p, c, fit_seer, continuous, find_lineage, lin, err):
+    """find_enet_selected without a second pass over the input: `rows` are the matrix's rows of the columns with a non-zero slope
+    (EnetMatrix.get_rows, fetched before the matrix was closed), in stream order; names = (blob, offsets) and counts are theirs.  A row
+    stored by its absences (2 * count > n) is complemented back over the n samples."""
+    from .input import strains_from_bits
+    n = len(p)
+    samples = [str(x) for x in p.index]
+    order = sorted(range(n), key=lambda i: samples[i])
+    blob, off = names
+    tail = np.zeros(rows.shape[1] * 8, dtype=np.uint8)
+    tail[:n] = 1
+    valid = np.packbits(tail, bitorder="little")
+    for i, beta in enumerate(enet_betas):
+        row = rows[i]
+        if 2 * int(counts[i]) > n:
+            row = ~row & valid
+        var_name = bytes(blob[off[i]:off[i + 1]]).decode()
+        kstrains, nkstrains = strains_from_bits(row, order, samples)
+        if len(kstrains) == 0:                                        # (read_variant says so whenever it parses such a line)
+            err.write("No observations of " + var_name + " in selected samples\n")
+        k = np.unpackbits(row, bitorder="little")[:n].astype(np.int64)
+        yield _enet_row(var_name, k, float(int(counts[i])) / n, kstrains, nkstrains, beta, p, c, fit_seer, continuous, find_lineage, lin)
 
 
 def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_dict, clusters_full, dict_full, enet_seer, out, err):
@@ -284,16 +379,34 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
     kmers = list(options.kmers) if options.kmers else []
     var_type, var_file = ("kmers", kmers[0]) if kmers else (("vcf", options.vcf) if options.vcf else ("Rtab", options.pres))
     all_strains = set(p.index)
+    # k-mers come as raw blocks from the native reader or the packed cache and are filtered, coded and stored on the device
+    # (load_all_vars_blocks); --python-reader, --vcf and --pres go line by line through read_variant (load_all_vars)
+    native = bool(options.load_packed) or (var_type == "kmers" and not options.python_reader)
 
     def reopen():
         regions = collections.deque([]) if options.burden else None
         infile, sample_order = open_variant_file(var_type, var_file, options.burden, regions, options.uncompressed)
         return infile, sample_order, regions
+    names = counts = None
+    if native:
+        from .input import open_kmer_block_stream
+        blocks, cache_out = open_kmer_block_stream(options, p, kmers, max(options.block_size, 1 << 18))
     err.write("Reading all variants\n")
     engine = Engine(len(p), device=options.gpu)
-    infile, sample_order, regions = reopen()
-    M, var_indices, loaded = load_all_vars(engine, var_type, p, bool(options.burden), regions, infile, all_strains, sample_order,
-                                           options.min_af, options.max_af, options.max_missing, options.uncompressed)
+    if native:
+        try:
+            M, var_indices, loaded, blob, off, counts = load_all_vars_blocks(engine, p, blocks, options.min_af, options.max_af, options.max_missing)
+        except ValueError:                                            # (no line passed: the input was read to its end all the same)
+            if cache_out is not None:
+                cache_out.close()
+            raise
+        names = (blob, off)
+        if cache_out is not None:
+            cache_out.close()                                         # (the whole input has been read: the cache is complete)
+    else:
+        infile, sample_order, regions = reopen()
+        M, var_indices, loaded = load_all_vars(engine, var_type, p, bool(options.burden), regions, infile, all_strains, sample_order,
+                                               options.min_af, options.max_af, options.max_missing, options.uncompressed)
     var_indices = np.array(var_indices)
     pv = p.values.astype(float)
     if options.cor_filter > 0:
@@ -303,6 +416,8 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
             raise ValueError("No variants passed filters")
         M.keep(keep)
         var_indices = var_indices[keep]
+        if native:
+            names, counts = _take_names(names[0], names[1], keep), counts[keep]
     tested = len(var_indices)
     prefilter = loaded - tested
     weights, fold_ids = np.ones(len(p)), None
@@ -347,14 +462,22 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
         header += ['k-samples', 'nk-samples']
     header.append('notes')
     out.write('\t'.join(header) + "\n")
+    fit_seer = (m, null_fit, firth_null) if enet_seer else None
+    if native:
+        # the selected variants are resident: their rows come back from the matrix, no input is read a second time
+        sel = np.nonzero(betas[cov.shape[1] + 1:])[0]
+        sel_rows = M.get_rows(sel)
+        selected = selected_from_rows(betas[cov.shape[1] + 1:][sel], sel_rows, _take_names(names[0], names[1], sel), counts[sel], p, cov, fit_seer,
+                                      options.continuous, bool(options.lineage), lineage_clusters, err)
     M.close()
     engine.close()
-    infile, sample_order, regions = reopen()
+    if not native:
+        infile, sample_order, regions = reopen()
+        selected = find_enet_selected(betas, var_indices, p, cov, var_type, fit_seer, bool(options.burden), regions, infile, all_strains,
+                                      sample_order, options.continuous, bool(options.lineage), lineage_clusters, options.uncompressed)
     printed = 0
     label = (lineage_dict if lineage_dict is not None else []) if lineage_col else None
-    for x in find_enet_selected(betas, var_indices, p, cov, var_type, (m, null_fit, firth_null) if enet_seer else None, bool(options.burden),
-                                regions, infile, all_strains, sample_order, options.continuous, bool(options.lineage), lineage_clusters,
-                                options.uncompressed):
+    for x in selected:
         printed += 1
         out.write(format_output(x, label, 'enet', options.print_samples) + "\n")
     return prefilter, tested, printed

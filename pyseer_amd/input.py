@@ -1381,3 +1381,75 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
 
     for blk in prefetched(finished(), depth=max(2, int(ahead))):
         yield blk
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the command line's k-mer stream: which of text, --load-packed and --packed-cache a run reads, shared by the per-variant run and --wg enet
+# ---------------------------------------------------------------------------------------------------------------
+def check_kmers_gzipped(paths):
+    """The reference's gzip.open raises on plain text (input.py:271-276); the native reader would read it, so the command line asks."""
+    for vf in paths:
+        with open(vf, "rb") as fh:
+            if fh.read(2) != b"\x1f\x8b":
+                sys.stderr.write("Not a gzipped file (%s): use --uncompressed for plain-text k-mers\n" % vf)
+                sys.exit(1)
+
+
+def plan_packed_cache(options, p, var_file, read_first_block=True):
+    """--packed-cache, the automatic form of --save-packed / --load-packed: one file next to the input, tied to it by size + mtime (a sidecar
+    stamp), and to the run by the sample list the cache itself stores.  Sets options.load_packed (a fresh cache is read) or
+    options.save_packed (one is written); returns the stamp (sidecar path, text) for the PackedCacheWriter, or None.
+    read_first_block: check the cache by reading its first block, as the per-variant run always has (which says "No observations of ..." for
+    that block's empty lines once more); False checks the header alone (check_packed_cache: the same errors, nothing on stderr)."""
+    cache_stamp = None
+    side = var_file + ".seerpack"
+    st = os.stat(var_file)
+    stamp = "%d %d" % (st.st_size, int(st.st_mtime))
+    fresh = False
+    try:
+        fresh = os.path.exists(side) and open(side + ".stamp").read().strip() == stamp
+    except (IOError, OSError):
+        fresh = False
+    if fresh and not packed_cache_complete(side):
+        sys.stderr.write("Packed cache %s is incomplete (an interrupted run); parsing %s again\n" % (side, var_file))
+        fresh = False
+    if fresh:
+        try:
+            if read_first_block:
+                next(iter(iter_packed_blocks_cached(p, side, options.min_af, options.max_af, 1)), None)    # header + sample list check
+            else:
+                check_packed_cache(p, side)
+            options.load_packed = side
+        except ValueError:
+            sys.stderr.write("Packed cache %s was written for other samples; parsing %s again\n" % (side, var_file))
+            fresh = False
+        except IOError as ex:
+            sys.stderr.write("Packed cache %s cannot be used (%s); parsing %s again\n" % (side, ex, var_file))
+            fresh = False
+    if not fresh:
+        # the cache is written to a temporary name and renamed when the run has read the whole input; the stamp follows the rename
+        # (PackedCacheWriter.close), so an interrupted run leaves neither
+        if os.access(os.path.dirname(os.path.abspath(side)) or ".", os.W_OK):
+            options.save_packed = side
+            cache_stamp = (side + ".stamp", stamp)
+        else:
+            sys.stderr.write("Cannot write a packed cache next to %s; continuing without\n" % var_file)
+    return cache_stamp
+
+
+def open_kmer_block_stream(options, p, kmer_files, block_size):
+    """The RawBlock stream of a run that takes every parsed line as it is (--wg enet: the device applies its own rule), from what the
+    command line names: --load-packed, --packed-cache, one or several --kmers files.  Returns (blocks, PackedCacheWriter or None): the
+    caller closes the writer once the stream has ended.  The cache is read through the page cache (device=None: no registered windows)."""
+    cache_out = cache_stamp = None
+    if not options.uncompressed and not options.load_packed:
+        check_kmers_gzipped(kmer_files)
+    if options.packed_cache and not options.load_packed and not options.save_packed:
+        cache_stamp = plan_packed_cache(options, p, kmer_files[0], read_first_block=False)
+    if options.load_packed:
+        return iter_packed_blocks_cached(p, options.load_packed, options.min_af, options.max_af, block_size, raw=True, device=None), None
+    if len(kmer_files) > 1:
+        return iter_packed_blocks_native_multi(p, kmer_files, options.min_af, options.max_af, block_size, raw=True), None
+    if options.save_packed:
+        cache_out = PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
+    return iter_packed_blocks_native(p, kmer_files[0], options.min_af, options.max_af, block_size, save_to=cache_out, raw=True), cache_out

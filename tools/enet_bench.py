@@ -3,7 +3,16 @@
 every row once, so its rate against the HBM roof is the yardstick of the streaming kernels), and the cross-validated fit (k_enet_cd
 coordinate steps per second, KKT rounds).  One JSON line per measurement; warm-up run first, then --repeats timed runs (median, min, max).
 
-    python tools/enet_bench.py --variants 100000 --samples 5000 --n-lambda 5"""
+    python tools/enet_bench.py --variants 100000 --samples 5000 --n-lambda 5
+
+--ingest times the load path of k-mer input instead: sh_enet_ingest alone on 2^18-row blocks of host memory with about half the rows
+kept, then enet.load_all_vars_blocks (the command line's load stage up to the correlations) from a packed cache written here, next to the
+bare walk over the cache's blocks.  --load-kmers FILE times the same stage from a gzipped k-mer text (--python-reader: through
+enet.load_all_vars, the line-by-line path) and reports the process's peak resident set.
+
+    python tools/enet_bench.py --ingest --variants 1048576 --samples 5000
+    python tools/enet_bench.py --write-kmers kmers.gz --variants 100000 --samples 5000          # synthetic text + kmers.gz.pheno
+    python tools/enet_bench.py --load-kmers kmers.gz --pheno kmers.gz.pheno [--python-reader]"""
 import argparse
 import json
 import os
@@ -30,8 +39,133 @@ def stats(ts):
     return dict(median_s=float(np.median(ts)), min_s=float(np.min(ts)), max_s=float(np.max(ts)), n=len(ts))
 
 
+def peak_rss_mb():
+    import resource
+    return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
+
+
+def ingest_stage(o):
+    import tempfile
+    import pandas as pd
+    from pyseer_amd.engine import Engine
+    from pyseer_amd.enet import EnetMatrix, load_all_vars_blocks
+    from pyseer_amd.input import PackedCacheWriter, iter_packed_blocks_cached
+    P, N, B = o.variants, o.samples, 1 << 18
+    rows = synth(P, N, 1)
+    counts = np.concatenate([np.unpackbits(rows[s:s + 20000], axis=1, bitorder="little").sum(axis=1) for s in range(0, P, 20000)]).astype(np.int32)
+    lo, hi = int(np.median(counts)), N                                # about half the rows are kept
+    kept = int(((counts >= lo) & (counts <= hi)).sum())
+    e = Engine(N)
+    ts = []
+    for r in range(o.repeats + 1):
+        M = EnetMatrix(e, kept)                                       # (no growth inside the timed part: that is the next line's)
+        t = time.perf_counter()
+        for s in range(0, P, B):
+            M.ingest(rows[s:s + B], lo, hi)
+        dt = time.perf_counter() - t
+        assert M.rows == kept
+        M.close()
+        if r:
+            ts.append(dt)
+    med = float(np.median(ts))
+    print(json.dumps(dict(what="sh_enet_ingest, 2^18-row blocks of host memory, capacity reserved", variants=P, samples=N, kept=kept, bytes=int(rows.nbytes),
+                          rows_per_s=P / med, gb_per_s=rows.nbytes / med / 1e9, **stats(ts))), flush=True)
+    ts = []
+    for r in range(o.repeats + 1):
+        M = EnetMatrix(e, 1)
+        t = time.perf_counter()
+        for s in range(0, P, B):
+            M.ingest(rows[s:s + B], lo, hi)
+        dt = time.perf_counter() - t
+        M.close()
+        if r:
+            ts.append(dt)
+    med = float(np.median(ts))
+    print(json.dumps(dict(what="sh_enet_ingest, the same from an initial capacity of 1 (the matrix grows)", variants=P, samples=N, kept=kept,
+                          rows_per_s=P / med, gb_per_s=rows.nbytes / med / 1e9, **stats(ts))), flush=True)
+    # the same rows as a packed cache (page cache warm after the write): the bare walk over its blocks, touching one byte per page, and the load
+    names = ("K%09d" % 0).encode()
+    p = pd.Series(np.zeros(N), index=["s%d" % i for i in range(N)])
+    with tempfile.TemporaryDirectory(dir=o.tmp) as d:
+        path = os.path.join(d, "bench.seerpack")
+        w = PackedCacheWriter(path, list(p.index))
+        for s in range(0, P, B):
+            nv = min(B, P - s)
+            w.write_block(names * nv, np.arange(nv + 1, dtype=np.int64) * len(names), counts[s:s + nv], rows[s:s + nv])
+        w.close()
+        ts = []
+        for r in range(o.repeats + 1):
+            t = time.perf_counter(); tot = 0
+            for blk in iter_packed_blocks_cached(p, path, 0.0, 1.0, B, raw=True, device=None):
+                tot += int(blk.bits.reshape(-1)[::4096].sum())
+            dt = time.perf_counter() - t
+            if r:
+                ts.append(dt)
+        med = float(np.median(ts))
+        print(json.dumps(dict(what="packed cache: walk over the blocks, one byte per page read", variants=P, samples=N, rows_per_s=P / med,
+                              gb_per_s=rows.nbytes / med / 1e9, **stats(ts))), flush=True)
+        min_af = (lo - 0.5) / N
+        ts = []
+        for r in range(o.repeats + 1):
+            t = time.perf_counter()
+            M, vi, loaded, _, _, _ = load_all_vars_blocks(e, p, iter_packed_blocks_cached(p, path, 0.0, 1.0, B, raw=True, device=None), min_af, 1.1, 0.05)
+            dt = time.perf_counter() - t
+            assert loaded == P and M.rows == kept
+            M.close()
+            if r:
+                ts.append(dt)
+        med = float(np.median(ts))
+        print(json.dumps(dict(what="load_all_vars_blocks from the packed cache (reader thread + ingest + names and counts)", variants=P, samples=N,
+                              kept=kept, rows_per_s=P / med, gb_per_s=rows.nbytes / med / 1e9, peak_rss_mb=peak_rss_mb(), **stats(ts))), flush=True)
+    e.close()
+
+
+def write_kmers(o):
+    """--write-kmers FILE: --variants lines of gzipped k-mer text over --samples samples s0, s1, ... (synth()'s AF mix), and FILE.pheno."""
+    import gzip
+    N, P = o.samples, o.variants
+    rng = np.random.default_rng(7)
+    tok = np.array([" s%d:1" % i for i in range(N)], dtype=object)
+    af = np.where(rng.random(P) < 0.7, rng.uniform(0.01, 0.1, P), rng.uniform(0.1, 0.5, P))
+    acgt = np.array(list("ACGT"))
+    with gzip.open(o.write_kmers, "wt", compresslevel=1) as f:
+        for s in range(0, P, 2000):
+            K = rng.random((min(2000, P - s), N)) < af[s:s + 2000, None]
+            names = rng.integers(0, 4, (K.shape[0], 31))
+            f.write("".join("".join(acgt[names[i]]) + " |" + "".join(tok[np.nonzero(K[i])[0]]) + "\n" for i in range(K.shape[0])))
+    with open(o.write_kmers + ".pheno", "w") as f:
+        f.write("samples\tbinary\n" + "".join("s%d\t%d\n" % (i, b) for i, b in enumerate(rng.integers(0, 2, N))))
+
+
+def load_kmers_stage(o):
+    from pyseer_amd.engine import Engine
+    from pyseer_amd.enet import load_all_vars, load_all_vars_blocks
+    from pyseer_amd.input import iter_packed_blocks_native, load_phenotypes, open_variant_file
+    p = load_phenotypes(o.pheno, None)
+    e = Engine(len(p))
+    t = time.perf_counter()
+    if o.python_reader:
+        infile, order = open_variant_file("kmers", o.load_kmers)
+        M, vi, loaded = load_all_vars(e, "kmers", p, False, None, infile, set(p.index), order, 0.01, 0.99, 0.05, False)
+    else:
+        M, vi, loaded = load_all_vars_blocks(e, p, iter_packed_blocks_native(p, o.load_kmers, 0.0, 1.0, 1 << 18, raw=True), 0.01, 0.99, 0.05)[:3]
+    dt = time.perf_counter() - t
+    t = time.perf_counter(); M.correlations(p.values.astype(float)); dc = time.perf_counter() - t
+    print(json.dumps(dict(what="load stage from gzipped k-mer text, %s" % ("load_all_vars (--python-reader)" if o.python_reader else "native reader + load_all_vars_blocks"),
+                          lines=int(loaded), kept=int(M.rows), samples=len(p), seconds=dt, lines_per_s=loaded / dt, correlations_s=dc,
+                          peak_rss_mb=peak_rss_mb())), flush=True)
+    M.close()
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ingest", action="store_true", help="the load path: sh_enet_ingest alone and from a packed cache")
+    ap.add_argument("--load-kmers", default=None, help="time the load stage from this gzipped k-mer file (needs --pheno)")
+    ap.add_argument("--pheno", default=None)
+    ap.add_argument("--write-kmers", default=None, help="write --variants lines of synthetic gzipped k-mer text (and FILE.pheno) and stop: no device needed")
+    ap.add_argument("--python-reader", action="store_true")
+    ap.add_argument("--tmp", default=None, help="directory for the packed cache of --ingest")
     ap.add_argument("--variants", type=int, default=100000)
     ap.add_argument("--samples", type=int, default=5000)
     ap.add_argument("--n-folds", type=int, default=10)
@@ -42,6 +176,12 @@ def main():
     ap.add_argument("--no-fit", action="store_true", help="the streaming kernels only")
     ap.add_argument("--continuous", action="store_true")
     o = ap.parse_args()
+    if o.write_kmers:
+        return write_kmers(o)
+    if o.ingest:
+        return ingest_stage(o)
+    if o.load_kmers:
+        return load_kmers_stage(o)
     from pyseer_amd.engine import Engine
     from pyseer_amd.enet import EnetMatrix, assign_folds
     P, N = o.variants, o.samples
