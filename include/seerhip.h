@@ -422,6 +422,32 @@ int     sh_enet_betas_at(sh_ctx *ctx, int problem, int i_lambda, double *beta0, 
 int     sh_enet_eta_at(sh_ctx *ctx, int i_lambda, double *eta);
 int     sh_enet_end(sh_ctx *ctx);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prediction from a saved elastic-net model (csrc/enet_kernels.hip k_enet_predict + csrc/enet_api.inc, csrc/nameset.cpp; replaces the loop
+ * of pyseer/enet_predict.py:159-179).
+ *   sh_predict_begin: a resident fp64 accumulator of n_samples, initialised from start[n_samples] (the intercept plus the covariate terms,
+ *     the caller's).  sh_predict_add: for k = 0 .. n_sel-1 in this order, acc[i] = acc[i] + k_i * beta[k] over every sample i, where k_i is
+ *     bit i of row row_idx[k] of the host block `present` (rows of row_bytes, layout of sh_lmm_batch; bits at and above n_samples are not
+ *     read as samples), complemented where flip[k] != 0; where `missing` (same shape, may be NULL) has the bit set, k_i is NaN for a row
+ *     that is not flipped and 0 for one that is.  The addend is the product, so a zero keeps numpy's sign.  Only the selected rows are
+ *     staged and uploaded; row_idx[k] must index a row of the block (the caller's check: the library is not told how many rows it holds).
+ *     Every sample's sum is sequential in the order of the calls and of row_idx: the bits of the result do not depend on how the rows are
+ *     split over calls.  sh_predict_end: copies the accumulator to link[n_samples] (may be NULL) and frees it.
+ *   sh_nameset_*: the model's names (one blob, n + 1 offsets) as a hash set on the host.  match: the rows v of a block's names (blob, V + 1
+ *     offsets) whose name is in the set and has not been met before, in block order -> row_idx[], and which name -> model_idx[] (V entries
+ *     each, the caller's); returns their number, or -1 for bad arguments.  A name is retired at its first hit (the reference pops it), so a
+ *     second line of the same name is not returned.  left: names not met yet.  One thread, no device.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sh_nameset sh_nameset;
+int         sh_predict_begin(sh_ctx *ctx, const double *start);
+int         sh_predict_add(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, const int64_t *row_idx, const double *beta,
+                           const uint8_t *flip, int64_t n_sel);
+int         sh_predict_end(sh_ctx *ctx, double *link);
+sh_nameset *sh_nameset_new(const char *blob, const int64_t *off, int64_t n);
+int64_t     sh_nameset_match(sh_nameset *set, const char *blob, const int64_t *off, int64_t V, int64_t *row_idx, int32_t *model_idx);
+int64_t     sh_nameset_left(const sh_nameset *set);
+void        sh_nameset_free(sh_nameset *set);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,7 +131,9 @@ def get_options(argv=None):
     wg.add_argument('--sequence-reweighting', action='store_true', help='Use --lineage-clusters to downweight sequences.')
     wg.add_argument('--save-vars', help='(not built: pickles of the reference)')
     wg.add_argument('--load-vars', help='(not built: pickles of the reference)')
-    wg.add_argument('--save-model', help='(not built: pickles of the reference)')
+    wg.add_argument('--save-model', help='(not built: pickles of the reference; --save-enet-model writes the model as text)')
+    wg.add_argument('--save-enet-model', default=None, help='File to save the fitted elastic net to, as text, for python -m pyseer_amd.enet_predict '
+                                                            '[Default: do not save the model]')
     wg.add_argument('--save-predictions', default=None, help='File to save predictions to in TSV format [Default: do not save predictions]')
     wg.add_argument('--alpha', type=float, default=0.0069, help='Set the mixing between l1 and l2 penalties [Default: 0.0069]')
     wg.add_argument('--n-folds', type=int, default=10, help='Number of folds cross-validation to perform [Default: 10]')
@@ -213,7 +215,8 @@ def main(argv=None):
     if options.wg:
         for name_, val_ in (('--save-vars', options.save_vars), ('--load-vars', options.load_vars), ('--save-model', options.save_model)):
             if val_:
-                _die('%s writes pickles of reference-internal objects and is not built in pyseer_amd\n' % name_)
+                _die('%s writes pickles of reference-internal objects and is not built in pyseer_amd\n' % name_ +
+                     ('--save-enet-model FILE writes the fitted model as text for python -m pyseer_amd.enet_predict\n' if name_ == '--save-model' else ''))
         if options.gpus is not None or options.packed_part:
             _die('--wg enet runs on one device: --gpus and --packed-part are not available with it\n')
         if (options.load_packed or options.save_packed or options.packed_cache or (options.kmers and len(options.kmers) > 1)) and \

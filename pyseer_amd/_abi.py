@@ -118,6 +118,14 @@ SIGNATURES = {
     "sh_enet_betas_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_dp]),
     "sh_enet_eta_at": (C.c_int, [C.c_void_p, C.c_int, c_dp]),
     "sh_enet_end": (C.c_int, [C.c_void_p]),
+    # prediction from a saved elastic-net model (k_enet_predict, csrc/enet_api.inc; the name set is csrc/nameset.cpp, host only)
+    "sh_predict_begin": (C.c_int, [C.c_void_p, c_dp]),
+    "sh_predict_add": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.POINTER(C.c_int64), c_dp, c_u8p, C.c_int64]),
+    "sh_predict_end": (C.c_int, [C.c_void_p, c_dp]),
+    "sh_nameset_new": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_int64), C.c_int64]),
+    "sh_nameset_match": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "sh_nameset_left": (C.c_int64, [C.c_void_p]),
+    "sh_nameset_free": (None, [C.c_void_p]),
 }
 
 

@@ -65,6 +65,7 @@ hipError_t shk_enet_moments(hipStream_t, const uint64_t *, int64_t, int, int, co
 hipError_t shk_enet_grad(hipStream_t, const uint64_t *, int64_t, int, const double *, int64_t, int, double *, int64_t);
 size_t shk_enet_cd_lds_bytes(int, int);
 hipError_t shk_enet_cd(hipStream_t, const struct EnetCdArgs *, int);
+hipError_t shk_enet_predict(hipStream_t, const uint64_t *, const uint64_t *, const double *, const uint8_t *, int64_t, int, int, double *);
 }
 #include "glm_api.inc"
 
@@ -102,6 +103,7 @@ template <typename T> static hipError_t dmalloc(T **p, size_t n)
 
 struct sh_lanes;
 struct EnetState;                        // enet_api.inc
+struct PredictState;                     // enet_api.inc
 // what sh_glm_setup was called with: the lanes of the context (lanes_api.inc) are set up from it
 struct GlmSetupArgs { std::vector<double> y, W; int q = 0, continuous = 0, force_firth = 0; double null_llf = 0, null_firth = 0, pret = 1, lrtt = 1;
                       std::string route; };   // (route: the SEERHIP_ROUTE string the set-up ran under)
@@ -176,6 +178,8 @@ struct sh_ctx {
     uint8_t *d_bits = nullptr; double *d_out = nullptr; uint32_t *d_flags = nullptr;
     // ---- the whole-genome elastic net's resident bit matrix and last fit (sh_enet_*)
     EnetState *enet = nullptr;
+    // ---- the accumulator of a saved model's predictions (sh_predict_*)
+    PredictState *predict = nullptr;
 };
 
 // ---- small device -> host read-backs (list lengths, counts) WITHOUT the copy engine ------------------------------------------------------------
@@ -198,6 +202,7 @@ static int readback_sync(sh_ctx *c, hipStream_t st, const int *a, const int *b, 
 
 static void lanes_destroy(sh_ctx *c);
 static void enet_free(sh_ctx *c);
+static void predict_free(sh_ctx *c);
 static int lanes_wait(sh_ctx *c);
 static void lanes_set_timing(sh_ctx *c, int on);
 static int lanes_add_timing(sh_ctx *c, double *total_ms, int64_t *launches);
@@ -563,6 +568,7 @@ void sh_destroy(sh_ctx *c)
     hipSetDevice(c->device);
     lanes_destroy(c);
     enet_free(c);
+    predict_free(c);
     free_ws(c);
     if (c->h_nkeep) hipHostFree(c->h_nkeep);
     if (c->h_rb) hipHostFree(c->h_rb);

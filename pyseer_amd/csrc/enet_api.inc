@@ -442,3 +442,86 @@ int sh_enet_eta_at(sh_ctx *c, int i_lambda, double *eta)
     std::copy(e->eta.begin() + (size_t)i_lambda * e->N, e->eta.begin() + (size_t)(i_lambda + 1) * e->N, eta);
     return SH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// sh_predict_*: a saved model applied to new samples (pyseer/enet_predict.py:159-185).  One fp64 accumulator of n_samples stays on the device
+// between sh_predict_begin and sh_predict_end; sh_predict_add adds the selected rows of a host block to it, in the order given.
+extern "C++" {
+struct PredictState {
+    double *d_acc = nullptr;
+    uint8_t *h_stage = nullptr, *d_stage = nullptr; size_t stage_bytes = 0;     // pinned host staging and its device twin
+};
+}
+#define PREDICT_STAGE_BYTES ((size_t)32 << 20)                       // rows of one upload: what fits 32 MB (one row at least)
+
+static void predict_free(sh_ctx *c)
+{
+    if (!c->predict) return;
+    hipFree(c->predict->d_acc); hipFree(c->predict->d_stage);
+    if (c->predict->h_stage) hipHostFree(c->predict->h_stage);
+    delete c->predict; c->predict = nullptr;
+}
+
+int sh_predict_begin(sh_ctx *c, const double *start)
+{
+    if (!c || !start) return fail(SH_EINVAL, "sh_predict_begin: null argument");
+    HIPCHK(hipSetDevice(c->device));
+    predict_free(c);
+    c->predict = new PredictState();
+    if (hipMalloc((void **)&c->predict->d_acc, (size_t)c->N * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); predict_free(c); return fail(SH_ENOMEM, "sh_predict_begin: no room for the accumulator"); }
+    const hipError_t rc = hipMemcpy(c->predict->d_acc, start, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice);
+    if (rc != hipSuccess) { predict_free(c); return fail(SH_EHIP, std::string("sh_predict_begin: ") + hipGetErrorString(rc)); }
+    return SH_OK;
+}
+
+int sh_predict_add(sh_ctx *c, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, const int64_t *row_idx, const double *beta, const uint8_t *flip,
+                   int64_t n_sel)
+{
+    if (!c || !c->predict) return fail(SH_EINVAL, "sh_predict_add before sh_predict_begin");
+    if (n_sel < 0 || row_bytes <= 0 || row_bytes % 8 || row_bytes * 8 < c->N) return fail(SH_ESHAPE, "sh_predict_add: row_bytes must be a multiple of 8 covering n_samples");
+    if (n_sel == 0) return SH_OK;
+    if (!present || !row_idx || !beta || !flip) return fail(SH_EINVAL, "sh_predict_add: null argument");
+    for (int64_t k = 0; k < n_sel; ++k) if (row_idx[k] < 0) return fail(SH_ESHAPE, "sh_predict_add: negative row index");
+    PredictState *p = c->predict;
+    HIPCHK(hipSetDevice(c->device));
+    // one staged row: its present words, its missing words (if any), its slope and its flip, each kind contiguous over the chunk
+    const size_t per_row = (size_t)row_bytes * (missing ? 2 : 1) + sizeof(double) + 1;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_sel, (int64_t)(PREDICT_STAGE_BYTES / per_row)));
+    const size_t need = (size_t)chunk * per_row + 16;
+    if (need > p->stage_bytes) {
+        hipFree(p->d_stage); p->d_stage = nullptr; if (p->h_stage) hipHostFree(p->h_stage); p->h_stage = nullptr; p->stage_bytes = 0;
+        if (hipHostMalloc((void **)&p->h_stage, need, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&p->d_stage, need) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p->h_stage) hipHostFree(p->h_stage); p->h_stage = nullptr; hipFree(p->d_stage); p->d_stage = nullptr;
+            return fail(SH_ENOMEM, "sh_predict_add: no room for the staging buffers");
+        }
+        p->stage_bytes = need;
+    }
+    const int NW = (int)(row_bytes / 8);
+    for (int64_t s = 0; s < n_sel; s += chunk) {
+        const int64_t n = std::min(chunk, n_sel - s);
+        const size_t o_miss = (size_t)n * row_bytes, o_beta = o_miss + (missing ? (size_t)n * row_bytes : 0), o_flip = o_beta + (size_t)n * sizeof(double);
+        for (int64_t k = 0; k < n; ++k) {
+            memcpy(p->h_stage + (size_t)k * row_bytes, present + (size_t)row_idx[s + k] * row_bytes, (size_t)row_bytes);
+            if (missing) memcpy(p->h_stage + o_miss + (size_t)k * row_bytes, missing + (size_t)row_idx[s + k] * row_bytes, (size_t)row_bytes);
+        }
+        memcpy(p->h_stage + o_beta, beta + s, (size_t)n * sizeof(double));
+        memcpy(p->h_stage + o_flip, flip + s, (size_t)n);
+        HIPCHK(hipMemcpyAsync(p->d_stage, p->h_stage, o_flip + (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(shk_enet_predict(c->stream, reinterpret_cast<const uint64_t *>(p->d_stage), missing ? reinterpret_cast<const uint64_t *>(p->d_stage + o_miss) : nullptr,
+                                reinterpret_cast<const double *>(p->d_stage + o_beta), p->d_stage + o_flip, n, NW, c->N, p->d_acc));
+        HIPCHK(hipStreamSynchronize(c->stream));                      // (the staging buffer is free again; the sums of this chunk precede the next one's)
+    }
+    return SH_OK;
+}
+
+int sh_predict_end(sh_ctx *c, double *link)
+{
+    if (!c || !c->predict) return fail(SH_EINVAL, "sh_predict_end before sh_predict_begin");
+    hipSetDevice(c->device);
+    hipError_t rc = hipStreamSynchronize(c->stream);
+    if (rc == hipSuccess && link) rc = hipMemcpy(link, c->predict->d_acc, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost);
+    predict_free(c);
+    if (rc != hipSuccess) return fail(SH_EHIP, std::string("sh_predict_end: ") + hipGetErrorString(rc));
+    return SH_OK;
+}

@@ -10,6 +10,7 @@
 //   k_enet_cd           cyclic coordinate descent over a problem's active list, one persistent workgroup per problem, per-sample state in LDS
 //                       (or in a global buffer of the same layout when N is too large); binomial by IRLS inside the same workgroup
 //   k_enet_gather       rows idx[] of B, compacted (sh_enet_keep, and the rows of the selected variants for the per-variant engine)
+//   k_enet_predict      a saved model applied to new samples (pyseer/enet_predict.py:159-179): acc[sample] += bit * beta, row after row
 // State kept per sample: v (working weight), Rr (working residual r = Rr - o; the centring of the standardised columns is carried in the scalar
 // o, so a coordinate step touches the carriers only, as glmnet does for sparse input), and for binomial the working response z.
 #include <hip/hip_runtime.h>
@@ -363,7 +364,53 @@ __global__ __launch_bounds__(ENET_TPB) void k_enet_cd(EnetCdArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
+// k_enet_predict: the sum of pyseer/enet_predict.py:174-179 for the rows of one call, `predictions += k * pred_beta` row after row.
+// One lane owns one sample and keeps its sum in a register; a wavefront owns word blockIdx.x of every row, so the word, the slope and the
+// flip of a row are the same for all 64 lanes (scalar loads, one per 64 samples).  The order of the additions is the order of the rows and
+// nothing else: no atomics, no split of the row loop, so every sample's sum is the reference's sequential fp64 sum.  The addend is the
+// PRODUCT (double)k * beta, as in the reference, not a conditional add: 0 * beta keeps the sign of the zero that numpy adds.  A missing call
+// is NaN where the row is taken as it is and 0 where it is flipped (af > 0.5: ~np.array(k, dtype=bool) of a NaN is False).
+// Rows come eight at a time so that the loads of a group are in flight together; the adds stay in row order.
+template <bool HAS_MISSING>
+__global__ void __launch_bounds__(64) k_enet_predict(const uint64_t *__restrict__ rows, const uint64_t *__restrict__ miss, const double *__restrict__ beta,
+                                                    const uint8_t *__restrict__ flip, int64_t n_rows, int NW, int N, double *__restrict__ acc)
+{
+    const int wd = blockIdx.x, lane = threadIdx.x;
+    const int sample = wd * 64 + lane;                                // (bits at and above N belong to nobody: their lanes store nothing)
+    double a = sample < N ? acc[sample] : 0.0;
+    auto step = [&](uint64_t w, uint64_t m, double b, uint32_t f) {
+        const uint32_t bit = ((uint32_t)(w >> lane) & 1u) ^ f;
+        double k = (double)bit;
+        if (HAS_MISSING && ((m >> lane) & 1ull)) k = f ? 0.0 : __longlong_as_double(0x7ff8000000000000ll);
+        a = a + k * b;
+    };
+    int64_t r = 0;
+    for (; r + 8 <= n_rows; r += 8) {
+        uint64_t w[8], m[8]; double b[8]; uint32_t f[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            w[u] = rows[(r + u) * NW + wd]; m[u] = HAS_MISSING ? miss[(r + u) * NW + wd] : 0ull;
+            b[u] = beta[r + u]; f[u] = flip[r + u] ? 1u : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) step(w[u], m[u], b[u], f[u]);
+    }
+    for (; r < n_rows; ++r) step(rows[r * NW + wd], HAS_MISSING ? miss[r * NW + wd] : 0ull, beta[r], flip[r] ? 1u : 0u);
+    if (sample < N) acc[sample] = a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
 extern "C" {
+// n_rows rows of NW words (and their missing rows, or NULL), slopes and flips on the device -> acc[0 .. N); NW * 64 >= N is the caller's check
+hipError_t shk_enet_predict(hipStream_t st, const uint64_t *rows, const uint64_t *miss, const double *beta, const uint8_t *flip, int64_t n_rows, int NW, int N,
+                            double *acc)
+{
+    if (n_rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((N + 63) / 64)), block(64);
+    if (miss) hipLaunchKernelGGL(k_enet_predict<true>, grid, block, 0, st, rows, miss, beta, flip, n_rows, NW, N, acc);
+    else hipLaunchKernelGGL(k_enet_predict<false>, grid, block, 0, st, rows, miss, beta, flip, n_rows, NW, N, acc);
+    return hipGetLastError();
+}
 hipError_t shk_enet_store(hipStream_t st, const uint8_t *present, const uint8_t *missing, const uint8_t *flip, int64_t V, int NW, int N, uint64_t *dst)
 {
     if (V <= 0) return hipSuccess;

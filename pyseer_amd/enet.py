@@ -286,6 +286,8 @@ def write_lineage_predictions(true_values, predictions, fold_ids, lineage_dict, 
     out.write("\t".join(['Lineage', 'Size', 'R2']) + ("" if continuous else "\t" + "\t".join(['TP', 'TN', 'FP', 'FN'])) + "\n")
     for fold in range(int(max(fold_ids)) + 1):
         idx = np.where(fold_ids == fold)[0]
+        if idx.size == 0:                                             # (enet_predict --true-values: a lineage none of whose samples has a true value)
+            continue
         y_true, y_pred = true_values[idx], predictions[idx].reshape(-1)
         fold_r2 = np.nan if np.all(y_true == y_true[0]) else _r2(y_true, y_pred)
         line = [lineage_dict[fold], str(idx.shape[0]), '%.3f' % fold_r2]
@@ -477,7 +479,198 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
                                       sample_order, options.continuous, bool(options.lineage), lineage_clusters, options.uncompressed)
     printed = 0
     label = (lineage_dict if lineage_dict is not None else []) if lineage_col else None
+    # the model of --save-enet-model (__main__.py:677-711): the intercept, the covariates with a slope (at the mean of their column over the
+    # training samples, from the same positions of `betas` as the lines above), the printed variants with the af and beta of their rows
+    pred_model = collections.OrderedDict([('intercept', (1, betas[0]))])
+    for beta, covariate in zip(betas[1:cov.shape[1] + 1], cov.columns):
+        if beta != 0:
+            pred_model[str(covariate)] = (float(np.mean(cov[covariate])), beta)
     for x in selected:
         printed += 1
         out.write(format_output(x, label, 'enet', options.print_samples) + "\n")
+        pred_model[x.kmer] = (x.af, x.kbeta)
+    if getattr(options, "save_enet_model", None):
+        write_model(options.save_enet_model, pred_model, options.continuous)
+        err.write("Saved enet model as " + options.save_enet_model + "\n")
     return prefilter, tested, printed
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the saved model and its predictor (python -m pyseer_amd.enet_predict; pyseer/enet_predict.py)
+# ---------------------------------------------------------------------------------------------------------------
+MODEL_MAGIC = "#pyseer_amd-enet-model"
+MODEL_VERSION = 1
+
+
+def write_model(fname, model, continuous):
+    """The model as text: a header line, then name<TAB>af<TAB>beta per entry of `model` (a mapping name -> (af, beta)) in its order.  Floats
+    are written with repr, so read_model returns the same bits.  A name may hold spaces (Rtab gene names), not a tab or a line break."""
+    with open(fname, "w", newline="\n") as fout:
+        fout.write("%s\tversion=%d\tcontinuous=%d\n" % (MODEL_MAGIC, MODEL_VERSION, 1 if continuous else 0))
+        for name, (af, beta) in model.items():
+            name = str(name)
+            if name == "" or "\t" in name or "\n" in name or "\r" in name:
+                raise ValueError("a model entry's name may not be empty or hold a tab or a line break: %r" % name)
+            fout.write("%s\t%s\t%s\n" % (name, repr(float(af)), repr(float(beta))))
+
+
+class _ModelUnpickler(object):
+    """pickle.Unpickler that admits what the reference's model needs -- a list of a dict of tuples of Python and numpy scalars and a bool --
+    and no other global: loading a model runs nobody's code."""
+    ALLOWED = {("collections", "OrderedDict"), ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"), ("numpy", "dtype"),
+               ("_codecs", "encode")}                                 # (protocol 2 writes the bytes of a numpy scalar as an encoded str)
+
+    @classmethod
+    def load(cls, fh):
+        import pickle
+
+        class Restricted(pickle.Unpickler):
+            def find_class(self, module, name):
+                if (module, name) in cls.ALLOWED:
+                    return pickle.Unpickler.find_class(self, module, name)
+                raise pickle.UnpicklingError("the model names the global %s.%s: refused (a model holds names and numbers only)" % (module, name))
+        return Restricted(fh).load()
+
+
+def read_model(fname):
+    """(OrderedDict name -> (af, beta), continuous) from the text form of write_model, or from the reference's pickle
+    ([{name: (af, beta), 'intercept': (1, b0)}, continuous], pyseer/__main__.py:705-711) through an unpickler that refuses every other global.
+    Raises ValueError for anything else."""
+    import collections
+    import pickle
+    with open(fname, "rb") as fh:
+        head = fh.read(2)
+        fh.seek(0)
+        if head[:1] == b"\x80":                                       # a pickle of protocol 2 and later begins with PROTO
+            try:
+                obj = _ModelUnpickler.load(fh)
+                model_dict, continuous = obj
+                model = collections.OrderedDict((str(k), (float(v[0]), float(v[1]))) for k, v in model_dict.items())
+            except pickle.UnpicklingError as e:
+                raise ValueError(str(e))
+            except Exception as e:
+                raise ValueError("%s is not a model pickle of [dict of (af, beta), continuous]: %s" % (fname, e))
+            return model, bool(continuous)
+        text = fh.read()
+    try:
+        lines = text.decode("utf-8").split("\n")
+    except UnicodeDecodeError:
+        raise ValueError("%s is neither a text model nor a pickle" % fname)
+    header = lines[0].split("\t")
+    if header[0] != MODEL_MAGIC or len(header) != 3 or header[1] != "version=%d" % MODEL_VERSION or header[2] not in ("continuous=0", "continuous=1"):
+        raise ValueError("%s does not begin with the header of a version %d model (%s)" % (fname, MODEL_VERSION, MODEL_MAGIC))
+    model = collections.OrderedDict()
+    for i, line in enumerate(lines[1:]):
+        if line == "":
+            continue
+        f = line.split("\t")
+        try:
+            if len(f) != 3 or f[0] == "":
+                raise ValueError
+            model[f[0]] = (float(f[1]), float(f[2]))                  # (a name given twice: the last stands, as in a dict)
+        except ValueError:
+            raise ValueError("%s line %d is not name<TAB>af<TAB>beta" % (fname, i + 2))
+    return model, header[2] == "continuous=1"
+
+
+class NameSet(object):
+    """The model's names as the library's hash set (sh_nameset_*): match() returns the rows of a block's name blob that are in the model and
+    were not met before, with the index of the name; a name is retired at its first hit."""
+
+    def __init__(self, names):
+        self._lib = _abi.load()
+        enc = [str(x).encode() for x in names]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in enc], out=off[1:])
+        h = self._lib.sh_nameset_new(b"".join(enc), off.ctypes.data_as(C.POINTER(C.c_int64)), len(enc))
+        if not h:
+            raise MemoryError("sh_nameset_new failed")
+        self._h = C.c_void_p(h)
+
+    def match(self, blob, off):
+        """blob: bytes or a uint8 array; off: V + 1 int64 offsets -> (row indices int64, model indices int32), in block order."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        V = off.size - 1
+        if V < 1:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        rows, which = np.empty(V, dtype=np.int64), np.empty(V, dtype=np.int32)
+        if isinstance(blob, np.ndarray):
+            keep = np.ascontiguousarray(blob, dtype=np.uint8)
+            ptr = C.c_void_p(keep.ctypes.data)
+        else:
+            keep = bytes(blob)
+            ptr = C.cast(C.c_char_p(keep), C.c_void_p)
+        n = self._lib.sh_nameset_match(self._h, ptr, off.ctypes.data_as(C.POINTER(C.c_int64)), V, rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       which.ctypes.data_as(C.POINTER(C.c_int32)))
+        if n < 0:
+            raise ValueError("sh_nameset_match: bad arguments")
+        return rows[:n], which[:n]
+
+    @property
+    def left(self):
+        return int(self._lib.sh_nameset_left(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sh_nameset_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EnetPredictor(object):
+    """The sum of pyseer/enet_predict.py:174-179 on the device of `engine` (sh_predict_*): an fp64 accumulator per sample that starts at
+    `start` and takes `k * beta` of every row added, in the order added."""
+
+    def __init__(self, engine, start):
+        self._e, self._lib, self._h = engine, engine._lib, engine._h
+        self.n = engine.n
+        self.row_bytes = row_bytes_for(self.n)
+        start = np.ascontiguousarray(start, dtype=float).reshape(-1)
+        if start.shape != (self.n,):
+            raise ValueError("start must hold one value per sample")
+        _abi.check(self._lib.sh_predict_begin(self._h, start.ctypes.data_as(_abi.c_dp)))
+        self._open = True
+
+    def add(self, block_bits, idx, beta, flip, missing=None):
+        """Rows idx[] of the packed block (V, row_bytes) with slopes beta[] and flips flip[], in this order; missing: the block's missing-call
+        rows (same shape) or None."""
+        bits = np.asarray(block_bits)
+        if bits.dtype != np.uint8 or bits.ndim != 2 or bits.shape[1] != self.row_bytes or not bits.flags.c_contiguous:
+            bits = np.ascontiguousarray(bits, dtype=np.uint8)
+            if bits.ndim != 2 or bits.shape[1] != self.row_bytes:
+                raise ValueError("packed rows must be (V, %d) bytes" % self.row_bytes)
+        V = bits.shape[0]
+        miss = None
+        if missing is not None:
+            miss = np.ascontiguousarray(missing, dtype=np.uint8)
+            if miss.shape != bits.shape:
+                raise ValueError("the missing rows must have the shape of the block")
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        beta = np.ascontiguousarray(beta, dtype=float).reshape(-1)
+        flip = np.ascontiguousarray(np.asarray(flip).reshape(-1) != 0, dtype=np.uint8)
+        if beta.shape != idx.shape or flip.shape != idx.shape:
+            raise ValueError("idx, beta and flip must have one entry per selected row")
+        if idx.size == 0:
+            return
+        if idx.min() < 0 or idx.max() >= V:
+            raise ValueError("row index outside the block")
+        _abi.check(self._lib.sh_predict_add(self._h, C.cast(bits.ctypes.data, _abi.c_u8p), None if miss is None else C.cast(miss.ctypes.data, _abi.c_u8p),
+                                            self.row_bytes, idx.ctypes.data_as(C.POINTER(C.c_int64)), beta.ctypes.data_as(_abi.c_dp),
+                                            flip.ctypes.data_as(_abi.c_u8p), idx.size))
+
+    def finish(self):
+        """The accumulator, (n,) float64; the predictor is closed."""
+        out = np.empty(self.n)
+        self._open = False
+        _abi.check(self._lib.sh_predict_end(self._h, out.ctypes.data_as(_abi.c_dp)))
+        return out
+
+    def close(self):
+        if self._open and self._e._h:
+            self._lib.sh_predict_end(self._h, None)
+        self._open = False

@@ -174,6 +174,10 @@ class VcfRecord(object):
         self.gt_index = fmt.index('GT') if 'GT' in fmt else -1
         self.fields = f[9:]
 
+    def name_all_alleles(self):
+        """contig_pos_ref_alt1_alt2...: the name pysam's alleles give a record with several ALTs (read_vcf_var, pyseer/input.py:470-471)."""
+        return self.name.replace(',', '_') if self.skip == VCF_MULTI else self.name
+
     def codes(self, n_cols, cache):
         """GT_* code of every sample column (a record with fewer fields than the header has columns: the rest are empty = missing)."""
         gi = self.gt_index
@@ -336,8 +340,11 @@ def read_variant(infile, p, var_type, burden, burden_regions, uncompressed, all_
     d = {}
     if var_type == "vcf":
         if not burden:
+            # (with a keep_list nothing of a record outside it is looked at, not even its ALT count: read_vcf_var, pyseer/input.py:473-478)
+            if keep_list is not None and line.name_all_alleles() not in keep_list:
+                return False, None, None, None, None, None, None
             var_name = infile.apply(line, d)
-            if var_name is None or (keep_list is not None and var_name not in keep_list):
+            if var_name is None:
                 return False, None, None, None, None, None, None
         else:
             var_name, regions = line
@@ -349,7 +356,8 @@ def read_variant(infile, p, var_type, burden, burden_regions, uncompressed, all_
                     sys.stderr.write("Could not parse region %s\n" % str(region))      # (the reference prints its failed match: None)
                     continue
                 for rec in infile.fetch(*region):
-                    infile.apply(rec, d)
+                    if keep_list is None or rec.name_all_alleles() in keep_list:      # (the reference hands the keep_list to the records of a region too)
+                        infile.apply(rec, d)
     elif var_type == "kmers":
         if not uncompressed:
             line = line.decode()
@@ -875,9 +883,10 @@ class RawBlock(object):
         return int(self.counts.shape[0])
 
 
-def _raw_block(blob, off, counts, bits, dma=False, release=None):
+def _raw_block(blob, off, counts, bits, dma=False, release=None, say_empty=True):
+    """say_empty=False: the consumer parses only some of the lines (enet_predict: those the model names) and says it for those itself."""
     off = np.require(off, dtype=np.int64, requirements=["A", "C"]); counts = np.require(counts, dtype=np.int32, requirements=["A", "C"])   # (views of a mapping may be misaligned)
-    for i in np.nonzero(counts == 0)[0]:                    # (read_variant's message, pyseer/input.py:441-443)
+    for i in (np.nonzero(counts == 0)[0] if say_empty else ()):   # (read_variant's message, pyseer/input.py:441-443)
         sys.stderr.write("No observations of " + bytes(blob[off[i]:off[i + 1]]).decode() + " in selected samples\n")
     return RawBlock(blob, off, counts, bits, dma, release)
 
@@ -915,7 +924,7 @@ def _block_from_raw(n, samples, order, names, blob, off, bits, counts, min_af, m
     return blk
 
 
-def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, save_to=None, raw=False):
+def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, save_to=None, raw=False, say_empty=True):
     """Same PackedBlock stream as iter_packed_blocks for k-mer files, fed by the native reader.  save_to: a PackedCacheWriter that
     receives every raw block (all parsed variants, before the AF filter).  raw: RawBlock objects for the job stream instead."""
     samples = [str(x) for x in p.index]
@@ -927,7 +936,7 @@ def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns
             if save_to is not None:
                 save_to.write_block(blob, off, counts, bits)
             if raw:
-                yield _raw_block(blob, off, counts, bits)
+                yield _raw_block(blob, off, counts, bits, say_empty=say_empty)
             else:
                 yield _block_from_raw(n, samples, order, None, blob, off, bits, counts, min_af, max_af, want_patterns, want_samples)
 
@@ -1242,7 +1251,8 @@ def check_packed_cache(p, path):
         raise IOError("packed cache row width mismatch")
 
 
-def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, part=None, raw=False, device=None, ahead=2):
+def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, part=None, raw=False, device=None, ahead=2,
+                              say_empty=True):
     """PackedBlock stream from a packed cache written by --save-packed; the samples (and their order) must be the run's own.
     Stored blocks are re-cut to about `block_size` variants (stored blocks are never split, only merged).
     part = (i, n): only range i of n contiguous ranges of the cache's rows (the multi-GPU job: one range per device,
@@ -1361,7 +1371,7 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
                 if raw and len(group) == 1:
                     blob, off, counts, bits, j = group[0]
                     dma, release = windows.take(j) if windows is not None else (False, None)
-                    yield _raw_block(blob, off, counts, bits, dma, release)
+                    yield _raw_block(blob, off, counts, bits, dma, release, say_empty=say_empty)
                     continue
                 if len(group) == 1:
                     blob, off, counts, bits, _ = group[0]
@@ -1372,7 +1382,7 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
                     counts = np.concatenate([g[2] for g in group])
                     bits = np.concatenate([g[3] for g in group], axis=0)
                 if raw:
-                    yield _raw_block(blob, off, counts, bits)
+                    yield _raw_block(blob, off, counts, bits, say_empty=say_empty)
                     continue
                 yield _block_from_raw(n, samples, order, None, blob, off, bits, counts, min_af, max_af, want_patterns, want_samples)
         finally:
