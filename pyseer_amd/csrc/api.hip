@@ -31,7 +31,8 @@ hipError_t shk_repack_bits(hipStream_t, const uint8_t *, int64_t, int64_t, int64
 hipError_t shk_lmm_linear(hipStream_t, int, const uint64_t *, int64_t, int, int, const double *, const double *,
                           const double *, const double *, const uint64_t *, const uint64_t *, int, const double *, LmmLinOut);
 hipError_t shk_lmm_build_tab(hipStream_t, const double *, const double *, const double *, const double *, int, int, int, int, double *);
-hipError_t shk_lmm_quadform(hipStream_t, int, const int8_t *, const uint64_t *, int64_t, int, int, int, double *, const int *, int, int64_t *);
+hipError_t shk_lmm_quadform(hipStream_t, int, const int8_t *, const uint64_t *, int64_t, int, int, int, double *, const int *, int, int64_t *, const int8_t *);
+hipError_t shk_lmm_ragged_image(hipStream_t, const int8_t *, int, int, int, int8_t *);
 hipError_t shk_lmm_refine(hipStream_t, int64_t, int64_t, int, int, int, int, const int8_t *, const uint64_t *, uint64_t *, double *, LmmLinOut,
                           const double *, LmmFinParams, double *, uint32_t *, LmmRefine);
 hipError_t shk_af_compact(hipStream_t, int, int64_t, LmmLinOut, LmmFinParams, int *, int *, const uint64_t *, int64_t, uint64_t *,
@@ -123,6 +124,8 @@ struct sh_ctx {
     double *d_vv = nullptr, *d_mdiag = nullptr, *d_yc = nullptr, *d_Qb = nullptr, *d_tab = nullptr;   // d_tab: nibble tables of (vv, mdiag)
     uint64_t *d_y1 = nullptr, *d_y0 = nullptr;
     int8_t *d_G = nullptr;
+    int8_t *d_ragA = nullptr; size_t rag_bytes = 0;   // compact image of the ragged rows (k_lmm_ragged_i8), or null: no such rows / SEERHIP_ROUTE ragged=0
+    int ragged = 1;
     double quant_scale = 0.0;
     size_t g_bytes = 0, tab_doubles = 0;
     int64_t macs_issued = 0;      // int8 MACs per variant of the last main-pass contraction (sh_lmm_info)
@@ -555,6 +558,7 @@ sh_ctx *sh_create(int device, int n_samples)
     sh_ctx *c = new sh_ctx();
     c->device = device; c->N = n_samples;
     if (const char *qv = sh_route("qf")) c->qf_variant = std::atoi(qv);
+    if (const char *rv = sh_route("ragged")) c->ragged = std::atoi(rv);
     if (const char *lv = sh_route("lanes")) c->n_lanes = std::max(1, std::min(8, std::atoi(lv)));
     if (const char *ac = sh_route("afcompact")) c->af_compact = std::atoi(ac);
     c->NT = (n_samples + 255) / 256; c->Np = c->NT * 256;
@@ -577,7 +581,7 @@ void sh_destroy(sh_ctx *c)
     hipFree(c->af_rep); hipFree(c->af_slot); hipFree(c->af_m); hipFree(c->af_cnt); hipFree(c->af_bits); hipFree(c->af_out); hipFree(c->af_flags);
     if (c->keep_ev) hipEventDestroy(c->keep_ev);
     hipFree(c->d_vv); hipFree(c->d_mdiag); hipFree(c->d_yc); hipFree(c->d_Qb); hipFree(c->d_y1); hipFree(c->d_y0); hipFree(c->d_tab);
-    hipFree(c->d_G); hipFree(c->d_bits); hipFree(c->d_out); hipFree(c->d_flags); hipFree(c->d_rcount); hipFree(c->d_bmax);
+    hipFree(c->d_G); hipFree(c->d_ragA); hipFree(c->d_bits); hipFree(c->d_out); hipFree(c->d_flags); hipFree(c->d_rcount); hipFree(c->d_bmax);
     for (int b = 0; b < 2; ++b) { hipFree(c->hb_bits[b]); hipFree(c->hb_out[b]); hipFree(c->hb_flags[b]); if (c->ev_h2d[b]) hipEventDestroy(c->ev_h2d[b]); if (c->ev_done[b]) hipEventDestroy(c->ev_done[b]); }
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     for (int b = 0; b < 2; ++b) if (c->hp_bits[b]) hipHostFree(c->hp_bits[b]);
@@ -765,8 +769,8 @@ int sh_lmm_setup(sh_ctx *c, const double *U, const double *S, int k, const doubl
     if (DP) { Qbp.assign((size_t)N * DP, 0.0); for (int i = 0; i < N; ++i) for (int e = 0; e < r; ++e) Qbp[(size_t)i * DP + e] = Qb[(size_t)i * D + e]; }
 
     // 5. device side: M = W sgn W^T (fp64 MFMA), diagonal, limbs
-    hipFree(c->d_vv); hipFree(c->d_mdiag); hipFree(c->d_yc); hipFree(c->d_Qb); hipFree(c->d_y1); hipFree(c->d_y0); hipFree(c->d_G); hipFree(c->d_tab);
-    c->d_vv = c->d_mdiag = c->d_yc = c->d_Qb = c->d_tab = nullptr; c->d_y1 = c->d_y0 = nullptr; c->d_G = nullptr;
+    hipFree(c->d_vv); hipFree(c->d_mdiag); hipFree(c->d_yc); hipFree(c->d_Qb); hipFree(c->d_y1); hipFree(c->d_y0); hipFree(c->d_G); hipFree(c->d_tab); hipFree(c->d_ragA);
+    c->d_vv = c->d_mdiag = c->d_yc = c->d_Qb = c->d_tab = nullptr; c->d_y1 = c->d_y0 = nullptr; c->d_G = nullptr; c->d_ragA = nullptr; c->rag_bytes = 0;
     const int NT = c->NT, L = n_limbs;
     const int NR = 2 * NT;                                   // 128-sample row tiles
     // E extra limbs below the L of the main pass (at most 7 in all: 0.49 * 256^7 is where fp64 itself ends); contracted only for the
@@ -793,6 +797,13 @@ int sh_lmm_setup(sh_ctx *c, const double *U, const double *S, int k, const doubl
     HIPCHK(hipMemsetAsync(d_M, 0, sizeof(double) * (size_t)Np * Np, st));
     HIPCHK(dmalloc(&d_Ef, (size_t)Np * Np)); HIPCHK(dmalloc(&d_px, Np)); HIPCHK(dmalloc(&d_py, Np)); HIPCHK(dmalloc(&d_nrm, NPOW));
     HIPCHK(shk_lmm_build_G(st, d_W, d_sgn, N, Np, kp, NR, Lt, E, d_M, c->d_mdiag, d_amax, c->d_G, d_Ef, d_px, d_py, d_nrm, NPOW));
+    // the ragged rows behind the last full 128-row tile, as their own small image of the main pass' limbs (k_lmm_ragged_i8; SEERHIP_ROUTE ragged=0:
+    // the wide kernel contracts them itself, as a narrow or a full segment)
+    if (LmmRagged rg; c->ragged && lmm_ragged_shape(N, L, &rg)) {
+        c->rag_bytes = lmm_ragged_bytes(rg);
+        HIPCHK(hipMalloc((void **)&c->d_ragA, c->rag_bytes));
+        HIPCHK(shk_lmm_ragged_image(st, c->d_G + (size_t)E * NR * (NR + 1) * 8192, N, NR, L, c->d_ragA));
+    }
     // certified bound on the spectral norm of the quantisation error (shk_spectral_bound: trace of its 2^(nsq+1)-th power by repeated squaring on
     // the fp64 matrix pipe; d_M is free again once its diagonal and the limbs are taken)
     const int nsq = Np <= 16384 ? 5 : Np <= 32768 ? 4 : 3;
@@ -845,7 +856,7 @@ int sh_lmm_info(sh_ctx *c, int *n_limbs, int64_t *macs, double *qscale)
     if (!c || !c->lmm_ready) return fail(SH_EINVAL, "sh_lmm_setup has not run");
     if (n_limbs) *n_limbs = c->L;
     // executed int8 MACs per variant: as issued by the last main-pass launch (k_lmm_quadform_i8w drops the 32-row sub-tiles of the last row tile
-    // that are padding), else the full tiles of k_lmm_quadform_i8: L * sum_I 2(I+1) tiles * (128 rows * 64), NR = 2*NT row tiles
+    // that are padding; a ragged row tile counts as k_lmm_ragged_i8 issues it, padding rows and columns included), else the full tiles of k_lmm_quadform_i8: L * sum_I 2(I+1) tiles * (128 rows * 64), NR = 2*NT row tiles
     if (macs) *macs = c->macs_issued > 0 ? c->macs_issued : (int64_t)c->L * (2 * c->NT) * (2 * c->NT + 1) * 128 * 64;
     if (qscale) *qscale = c->quant_scale;
     return SH_OK;
@@ -864,8 +875,8 @@ int sh_lmm_share(sh_ctx *dst, sh_ctx *src)
     HIPCHK(hipSetDevice(dst->device));
     sh_ctx *c = dst;
     const int N = c->N;
-    hipFree(c->d_vv); hipFree(c->d_mdiag); hipFree(c->d_yc); hipFree(c->d_Qb); hipFree(c->d_y1); hipFree(c->d_y0); hipFree(c->d_G); hipFree(c->d_tab);
-    c->d_vv = c->d_mdiag = c->d_yc = c->d_Qb = c->d_tab = nullptr; c->d_y1 = c->d_y0 = nullptr; c->d_G = nullptr; c->lmm_ready = false;
+    hipFree(c->d_vv); hipFree(c->d_mdiag); hipFree(c->d_yc); hipFree(c->d_Qb); hipFree(c->d_y1); hipFree(c->d_y0); hipFree(c->d_G); hipFree(c->d_tab); hipFree(c->d_ragA);
+    c->d_vv = c->d_mdiag = c->d_yc = c->d_Qb = c->d_tab = nullptr; c->d_y1 = c->d_y0 = nullptr; c->d_G = nullptr; c->d_ragA = nullptr; c->rag_bytes = 0; c->lmm_ready = false;
     HIPCHK(dmalloc(&c->d_vv, N)); HIPCHK(dmalloc(&c->d_mdiag, N)); HIPCHK(dmalloc(&c->d_yc, N));
     HIPCHK(dmalloc(&c->d_y1, c->NB64p)); HIPCHK(dmalloc(&c->d_y0, c->NB64p));
     if (src->DP) HIPCHK(dmalloc(&c->d_Qb, (size_t)N * src->DP));
@@ -876,6 +887,7 @@ int sh_lmm_share(sh_ctx *dst, sh_ctx *src)
     HIPCHK(cp(c->d_y1, src->d_y1, sizeof(uint64_t) * c->NB64p)); HIPCHK(cp(c->d_y0, src->d_y0, sizeof(uint64_t) * c->NB64p));
     if (src->DP) HIPCHK(cp(c->d_Qb, src->d_Qb, sizeof(double) * (size_t)N * src->DP));
     HIPCHK(cp(c->d_G, src->d_G, src->g_bytes)); HIPCHK(cp(c->d_tab, src->d_tab, sizeof(double) * src->tab_doubles));
+    if (src->d_ragA) { HIPCHK(hipMalloc((void **)&c->d_ragA, src->rag_bytes)); HIPCHK(cp(c->d_ragA, src->d_ragA, src->rag_bytes)); c->rag_bytes = src->rag_bytes; }
     HIPCHK(hipStreamSynchronize(dst->stream));
     c->k = src->k; c->D = src->D; c->L = src->L; c->DP = src->DP; c->E = src->E; c->complement = src->complement;
     c->quant_scale = src->quant_scale; c->err_norm_ulp = src->err_norm_ulp; c->err_norm_est_ulp = src->err_norm_est_ulp; c->err_norm_squarings = src->err_norm_squarings; c->trace_M = src->trace_M; c->lmm_tol = src->lmm_tol;
@@ -1018,10 +1030,10 @@ static int lmm_batch_dev_inner(sh_ctx *c, const void *d_bits, int64_t row_bytes,
     if (compact && nk > 0) {
         const int64_t Vpad2 = (nk + 511) / 512 * 512;
         HIPCHK(shk_af_compact(st, 1, V, lo, KP, c->d_keep, nullptr, c->d_T, Vpad, c->d_T2, Vpad2, c->NB64p, (int)nk, nullptr, nullptr));
-        HIPCHK(shk_lmm_quadform(st, c->qf_variant, Gmain, c->d_T2, Vpad2, 2 * c->NT, c->L, lsplit, c->d_q2, nullptr, c->N - (2 * c->NT - 1) * 128, &c->macs_issued));
+        HIPCHK(shk_lmm_quadform(st, c->qf_variant, Gmain, c->d_T2, Vpad2, 2 * c->NT, c->L, lsplit, c->d_q2, nullptr, c->N - (2 * c->NT - 1) * 128, &c->macs_issued, c->d_ragA));
         HIPCHK(shk_af_compact(st, 2, V, lo, KP, c->d_keep, nullptr, nullptr, Vpad, nullptr, Vpad2, lsplit, (int)nk, c->d_q2, c->d_q));
     } else if (!compact) {
-        HIPCHK(shk_lmm_quadform(st, c->qf_variant, Gmain, c->d_T, Vpad, 2 * c->NT, c->L, lsplit, c->d_q, nullptr, c->N - (2 * c->NT - 1) * 128, &c->macs_issued));
+        HIPCHK(shk_lmm_quadform(st, c->qf_variant, Gmain, c->d_T, Vpad, 2 * c->NT, c->L, lsplit, c->d_q, nullptr, c->N - (2 * c->NT - 1) * 128, &c->macs_issued, c->d_ragA));
     }
     if (c->timing) { HIPCHK(hipEventRecord(e1, st)); c->tev.emplace_back(e0, e1); }
     LmmFinParams P = c->fin; P.min_af = c->min_af; P.max_af = c->max_af; P.af_on = c->af_on;

@@ -590,6 +590,118 @@ __global__ __launch_bounds__(64 * QF_WAVES, QF_JT == 2 ? 2 : 1) void k_lmm_quadf
 #include "lmm_quadform_wide.inc"
 
 // ---------------------------------------------------------------------------------------------
+// The ragged rows.  N = 128 nf + r with a small r (5000 = 39 x 128 + 8): the wide kernel would spend a whole segment of narrow stages, per limb,
+// on r rows.  Their contraction is tiny -- all limbs stacked, L x rp rows (rp = r rounded up to 8) = one or two 32-row MFMA tiles against the
+// columns j < i -- so it runs here from a compact image of those rows (k_lmm_ragged_image, once per run) and the wide kernel stops at the last
+// full row tile.  One wavefront = 128 variants (four 32-column MFMA tiles), no LDS: a lane reads its A fragment (16 bytes, 1 KB per wavefront
+// and k-step, the whole image stays in L2) and its own half of the packed-bit word straight from memory, the next sample block's while the
+// MFMAs of this one issue; the variant fragments are expanded as in k_lmm_quadform_i8 (the image keeps the limb tiles' column order).
+// Epilogue: accumulator rows masked by the variant's own bits (samples 128 nf .. of word 2 nf), summed per limb over the registers and the two
+// lane halves, and ADDED, times 256^l, to the wide kernel's partial q[l * Vpad + v] by one thread per (limb, variant): both terms are exact
+// integers times 256^l far below 2^53, so q holds the very bits the one-kernel contraction writes.
+// ---------------------------------------------------------------------------------------------
+#define RG_LMAX 7                    // limbs of a main pass (sh_lmm_setup: 3 .. 7)
+
+__global__ __launch_bounds__(128) void k_lmm_ragged_image(const int8_t *__restrict__ G, int NR, int L, int nf, int rp, int nsb, int8_t *__restrict__ A)
+{
+    const int mt = blockIdx.y, sb = blockIdx.x;                       // grid = (sample block, MFMA row tile); thread = k-half x lane
+    const int kh = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5;
+    const int R = mt * 32 + l31, l = R / rp, s = R - l * rp;          // stacked row -> (limb, row of the ragged tile)
+    const int64_t TL = (int64_t)NR * (NR + 1);
+    uint4 o = make_uint4(0, 0, 0, 0);
+    if (l < L) o = *reinterpret_cast<const uint4 *>(G + ((int64_t)l * TL + (int64_t)nf * (nf + 1) + sb) * QF_TILE_BYTES + qf_off(s, lh + 2 * kh));
+    *reinterpret_cast<uint4 *>(A + (((int64_t)mt * nsb + sb) * 2 + kh) * 1024 + lane * 16) = o;
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void k_lmm_ragged_i8(const int8_t *__restrict__ A, const uint64_t *__restrict__ T, int64_t Vpad, int nsb, int nf,
+                                                       int rp, int mtot, int L, double *__restrict__ q)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, lh = lane >> 5;
+    const int64_t v0 = (int64_t)blockIdx.x * QF_BN + wave * 128 + l31;                     // this lane's variant of column tile 0 (+ 32 jt)
+    const uint32_t *th = reinterpret_cast<const uint32_t *>(T) + 2 * v0 + lh;            // ... its half (samples 32 lh ..) of a word
+    uint64_t wm[4];                                                                        // the ragged rows' own bits: the epilogue's mask
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) wm[jt] = T[(int64_t)(2 * nf) * Vpad + v0 + 32 * jt];
+    int ls[4][RG_LMAX];
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+        for (int l = 0; l < RG_LMAX; ++l) ls[jt][l] = 0;
+#pragma unroll 1
+    for (int mt0 = 0; mt0 < mtot; mt0 += MT) {
+        const v4i *ap = reinterpret_cast<const v4i *>(A) + (int64_t)mt0 * nsb * 128 + lane;   // 64 fragments per (row tile, sample block, k-half)
+        v16i acc[MT][4];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mt][jt][r] = 0;
+        // a ring of D register buffers (packed-bit halves + A fragments of one sample block each), D - 1 blocks of loads in flight while the
+        // MFMAs of the oldest issue; the ring is walked by a loop unrolled D times, so that every buffer has registers of its own (a rotation
+        // through copies is folded by hipcc into "load, then use at once") and sched_barrier keeps each block's loads in front of the MFMAs
+        constexpr int D = MT == 1 ? 4 : 2;
+        uint32_t h[D][4];
+        v4i a[D][MT][2];
+        auto load = [&](int sb, uint32_t (&hh)[4], v4i (&aa)[MT][2]) {
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) hh[jt] = th[2 * ((int64_t)sb * Vpad + 32 * jt)];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) { aa[mt][0] = ap[((int64_t)mt * nsb + sb) * 128]; aa[mt][1] = ap[((int64_t)mt * nsb + sb) * 128 + 64]; }
+        };
+#pragma unroll
+        for (int d = 0; d < D - 1; ++d) load(min(d, nsb - 1), h[d], a[d]);
+#pragma unroll 1
+        for (int sb0 = 0; sb0 < nsb; sb0 += D) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                load(min(sb0 + u + D - 1, nsb - 1), h[(u + D - 1) % D], a[(u + D - 1) % D]);     // (behind the last block: loaded again, never used)
+                __builtin_amdgcn_sched_barrier(0);
+                if (sb0 + u < nsb) {
+#pragma unroll
+                    for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+                        for (int jt = 0; jt < 4; ++jt) {
+                            const uint32_t x = h[u][jt] >> (4 * kh);
+                            const v4i b = (v4i){(int)(x & 0x01010101u), (int)((x >> 1) & 0x01010101u), (int)((x >> 2) & 0x01010101u), (int)((x >> 3) & 0x01010101u)};
+#pragma unroll
+                            for (int mt = 0; mt < MT; ++mt) acc[mt][jt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u][mt][kh], b, acc[mt][jt], 0, 0, 0);
+                        }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // registers 4 g .. 4 g + 3 = stacked rows (mt0 + mt) 32 + 8 g + 4 lh ..: four rows of ONE limb (rp is a multiple of 8)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int R = (mt0 + mt) * 32 + 8 * g + 4 * lh, l = R / rp, s = R - l * rp;
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt) {
+                    const uint32_t m4 = (uint32_t)(wm[jt] >> s);
+                    int sg = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) sg += ((m4 >> k) & 1u) ? acc[mt][jt][4 * g + k] : 0;
+#pragma unroll
+                    for (int x = 0; x < RG_LMAX; ++x) ls[jt][x] += (x == l) ? sg : 0;
+                }
+            }
+    }
+    double scale = 1.0;
+#pragma unroll
+    for (int l = 0; l < RG_LMAX; ++l) {
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            const int t = ls[jt][l] + __shfl_xor(ls[jt][l], 32, 64);          // lanes l and l ^ 32 hold different rows of the same variant
+            if (lh == 0 && l < L) { double *qo = q + (int64_t)l * Vpad + v0 + 32 * jt; *qo = fma((double)t, scale, *qo); }
+        }
+        scale *= 256.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Per-variant finalisation: a1 prefilter + A5 statistics + a7 filters (pyseer/lmm.py:160-217, 244-258).
 // ---------------------------------------------------------------------------------------------
 
@@ -1037,7 +1149,7 @@ hipError_t shk_lmm_linear(hipStream_t st, int DP, const uint64_t *T, int64_t Vpa
 }
 
 hipError_t shk_lmm_quadform(hipStream_t st, int variant, const int8_t *G, const uint64_t *T, int64_t Vpad, int NR, int L, int lsplit, double *q,
-                            const int *nlimit, int rows_last, int64_t *macs_per_variant)
+                            const int *nlimit, int rows_last, int64_t *macs_per_variant, const int8_t *ragA)
 {
     // the wide kernel's conditions: one limb per block, at least four row tiles (its DMA cursor runs four stages past the stream), 32-bit offsets
     const bool wide_ok = lsplit == L && NR >= 4 && (uint64_t)NR * 2 * (uint64_t)Vpad * 8 < (1ull << 32) && (uint64_t)(L + 1) * NR * (NR + 1) * QF_TILE_BYTES < (1ull << 32);
@@ -1051,8 +1163,16 @@ hipError_t shk_lmm_quadform(hipStream_t st, int variant, const int8_t *G, const 
     // rows_last = valid rows (samples) of the last 128-row tile; the wide kernel contracts only the 32-row sub-tiles that hold any (4, 2, 1, or none:
     // NR = 2 NT may exceed ceil(N / 128) by one).  The int8 MACs actually issued per variant go back to the caller (sh_lmm_info, the bench's roofline).
     const int nit_last = !wide ? 4 : rows_last <= 0 ? 0 : rows_last <= 32 ? 1 : rows_last <= 64 ? 2 : 4;
+    // The wide kernel is told how many full segments it runs and whether a narrow one follows.  ragA (the image of k_lmm_ragged_image, null where the
+    // sample count has no ragged tile or SEERHIP_ROUTE ragged=0 asks for the one-kernel route): the main pass stops at the last full row tile and
+    // k_lmm_ragged_i8 adds the remaining rows to its partial sums.
+    int nfull = nit_last == 4 ? NR : NR - 1, nit = nit_last == 4 ? 0 : nit_last;
+    LmmRagged rg;
+    const bool ragged = ragA && wide && variant != 464 && !nlimit && lmm_ragged_shape((NR - 1) * 128 + rows_last, L, &rg);
+    if (ragged) { nfull = rg.nf; nit = 0; }
     if (macs_per_variant)
-        *macs_per_variant = (int64_t)L * ((int64_t)(NR - 1) * NR * 128 * 64 + (int64_t)2 * NR * 32 * nit_last * 64);
+        *macs_per_variant = (int64_t)L * ((int64_t)nfull * (nfull + 1) * 128 * 64 + (int64_t)2 * (nfull + 1) * 32 * nit * 64)
+                            + (ragged ? (int64_t)rg.mt * 32 * rg.nsb * 64 : 0);
     const dim3 g((unsigned)(Vpad / QF_BN * lsplit)), b(wide ? 256 : 64 * QF_WAVES);
     const size_t lds = QF_NST * QF_STAGE_BYTES;
     static bool attr_set = false;
@@ -1094,19 +1214,33 @@ hipError_t shk_lmm_quadform(hipStream_t st, int variant, const int8_t *G, const 
     case 158: hipLaunchKernelGGL(k_lmm_quadform_i8<128>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit); break;   // no epilogue
     case 286: hipLaunchKernelGGL(k_lmm_quadform_i8<256>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit); break;   // no zeroing
     case 414: hipLaunchKernelGGL(k_lmm_quadform_i8<384>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit); break;   // neither
-    case 464: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 3>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;   // extra-limb pass
-    case 4: hipLaunchKernelGGL(k_lmm_quadform_i8w<0>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;        // wide wave tile
-    case 6: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break; // wide, s_memtime profile
-    case 7: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 0, 2>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break; // wide, s_memtime profile 2
-    case 8: hipLaunchKernelGGL((k_lmm_quadform_i8w<16, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break; // profile, no barrier
-    case 9: hipLaunchKernelGGL((k_lmm_quadform_i8w<1, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;  // profile, no DMA
-    case 50: hipLaunchKernelGGL(k_lmm_quadform_i8w<16>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;      // wide, no barrier
-    case 35: hipLaunchKernelGGL(k_lmm_quadform_i8w<1>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;       // wide, no DMA
-    case 162: hipLaunchKernelGGL(k_lmm_quadform_i8w<128>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;    // wide, no epilogue
-    case 441: hipLaunchKernelGGL(k_lmm_quadform_i8w<407>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit_last); break;    // wide, MFMAs only
+    case 464: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 3>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;   // extra-limb pass
+    case 4: hipLaunchKernelGGL(k_lmm_quadform_i8w<0>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;        // wide wave tile
+    case 6: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break; // wide, s_memtime profile
+    case 7: hipLaunchKernelGGL((k_lmm_quadform_i8w<0, 0, 2>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break; // wide, s_memtime profile 2
+    case 8: hipLaunchKernelGGL((k_lmm_quadform_i8w<16, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break; // profile, no barrier
+    case 9: hipLaunchKernelGGL((k_lmm_quadform_i8w<1, 0, 1>), g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;  // profile, no DMA
+    case 50: hipLaunchKernelGGL(k_lmm_quadform_i8w<16>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;      // wide, no barrier
+    case 35: hipLaunchKernelGGL(k_lmm_quadform_i8w<1>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;       // wide, no DMA
+    case 162: hipLaunchKernelGGL(k_lmm_quadform_i8w<128>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;    // wide, no epilogue
+    case 441: hipLaunchKernelGGL(k_lmm_quadform_i8w<407>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit, nit, nfull); break;    // wide, MFMAs only
     case 437: hipLaunchKernelGGL(k_lmm_quadform_i8<407>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit); break;   // MFMAs only
     default: hipLaunchKernelGGL(k_lmm_quadform_i8<0>, g, b, lds, st, G, T, Vpad, NR, L, lsplit, q, nlimit); break;
     }
+    if (ragged) {
+        const dim3 gr((unsigned)(Vpad / QF_BN)), br(256);
+        if (rg.mt == 1) hipLaunchKernelGGL(k_lmm_ragged_i8<1>, gr, br, 0, st, ragA, T, Vpad, rg.nsb, rg.nf, rg.rp, rg.mt, L, q);
+        else hipLaunchKernelGGL(k_lmm_ragged_i8<2>, gr, br, 0, st, ragA, T, Vpad, rg.nsb, rg.nf, rg.rp, rg.mt, L, q);
+    }
+    return hipGetLastError();
+}
+
+// the compact image of the ragged rows' main-pass limbs (G = the first of them), lmm_ragged_bytes() at ragA; N as in lmm_ragged_shape
+hipError_t shk_lmm_ragged_image(hipStream_t st, const int8_t *G, int N, int NR, int L, int8_t *ragA)
+{
+    LmmRagged rg;
+    if (!lmm_ragged_shape(N, L, &rg)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_lmm_ragged_image, dim3((unsigned)rg.nsb, (unsigned)rg.mt), dim3(128), 0, st, G, NR, L, rg.nf, rg.rp, rg.nsb, ragA);
     return hipGetLastError();
 }
 
@@ -1123,7 +1257,7 @@ hipError_t shk_lmm_refine(hipStream_t st, int64_t V, int64_t Vpad, int nq, int E
                           uint64_t *T3, double *q3, LmmLinOut li, const double *q, LmmFinParams P, double *out, uint32_t *flags, LmmRefine R)
 {
     hipLaunchKernelGGL(k_gather_T_list, dim3(64, (unsigned)NB64p), dim3(256), 0, st, T, Vpad, T3, R);
-    hipError_t e = shk_lmm_quadform(st, 64, Glow, T3, Vpad, NR, E, E, q3, R.count, 128, nullptr);
+    hipError_t e = shk_lmm_quadform(st, 64, Glow, T3, Vpad, NR, E, E, q3, R.count, 128, nullptr, nullptr);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lmm_refine_fix, dim3(64), dim3(256), 0, st, V, Vpad, nq, E, li, q, q3, P, out, flags, R);
     return hipGetLastError();

@@ -2,7 +2,7 @@
 // in the accumulator half of the unified register file (a[0:255]): half the LDS fragment reads per MFMA of k_lmm_quadform_i8 (4 ds_read_b128 per
 // 16 MFMAs instead of per 8).  Included by lmm_kernels.hip; same stage stream, LDS image, ring and epilogue arithmetic as k_lmm_quadform_i8 (see
 // the comments there); block = 512 variants, 4 waves x 128 variants; one limb per block (nl = 1), at least four row tiles (the launcher falls back
-// to k_lmm_quadform_i8 otherwise).
+// to k_lmm_quadform_i8 otherwise).  The launcher says how many segments run (`nfull`, `nit_last`): see the end of the kernel.
 //
 // Why inline assembly.  hipcc cannot hold 256 accumulators as C++ values here (its allocator copies all of them to VGPRs at every control-flow
 // join: the QF_JT = 4 build of round 1 spilled 187 registers inside the MFMA loop), and with one wavefront per SIMD nothing hides a badly placed
@@ -50,7 +50,7 @@ __device__ __forceinline__ void qw_read_bits(v2i_t (&H)[2][2], int h_addr)
 template <int ABL, int DM = 0, int PROF = 0>
 __global__ __launch_bounds__(256, 1) void k_lmm_quadform_i8w(const int8_t *__restrict__ G, const uint64_t *__restrict__ T,
                                                               int64_t Vpad, int NR, int L, int lsplit, double *__restrict__ qout,
-                                                              const int *__restrict__ nlimit, int nit_last)
+                                                              const int *__restrict__ nlimit, int nit_last, int nfull)
 {
     constexpr int JT = 4, DMA_PER_WAVE = 6;
     extern __shared__ __attribute__((aligned(16))) char smem[];       // QF_NST slots x 24 KB
@@ -93,6 +93,8 @@ __global__ __launch_bounds__(256, 1) void k_lmm_quadform_i8w(const int8_t *__res
     // offsets of the cursor's stage (two G tiles; the block's packed bits of the two 64-sample blocks they span).  The cursor runs QF_AHEAD stages
     // ahead and past the end of the stream by as much (into the next limb's tiles or the padding behind G; rows 0 .. 7 of T: NR >= 4 is the other
     // condition), so every stage issues the same six DMAs and the vmcnt arithmetic has no tail cases.
+    // Where the launcher stops the stream short of NR segments (padding row tiles; a ragged one left to k_lmm_ragged_i8) the cursor runs on into the
+    // next segment of the same limb: at least three segments run, so that one has four stages or more and spans rows 0 .. 7 of T at most.
     uint32_t gso = (uint32_t)((int64_t)lgrp * TL * QF_TILE_BYTES), tso = 0, prem = 1, plen = 2;
     const uint32_t tinc = (uint32_t)(2 * Vpad * 8);
     auto dma1 = [&](uint32_t lds_dst, uint32_t voff, const v4i &rs, uint32_t so) {
@@ -273,13 +275,14 @@ __global__ __launch_bounds__(256, 1) void k_lmm_quadform_i8w(const int8_t *__res
         }
         QW_STAMP(pt_epi)
     };
-    // nl = 1 (the launcher's condition): segment = row tile; the last one may be narrow or, when it is padding altogether, dropped
-    const int NRfull = (nit_last == 4) ? NR : NR - 1;
+    // nl = 1 (the launcher's condition): segment = row tile.  The launcher says how many of them run: `nfull` full ones (row tiles 0 .. nfull - 1) and,
+    // behind them, one narrow one (nit_last = 2 or 1 row sub-tiles) or none (0): row tiles that are padding altogether are dropped, and so is a
+    // ragged row tile that k_lmm_ragged_i8 contracts instead.  NR only describes the layout of G.
 #pragma unroll 1
-    for (int cI = 0; cI < NRfull; ++cI) segment(std::integral_constant<int, 4>{}, cI, scale0);
-    if (nit_last == 2) segment(std::integral_constant<int, 2>{}, NR - 1, scale0);
-    else if (nit_last == 1) segment(std::integral_constant<int, 1>{}, NR - 1, scale0);
-    const int total = nl * (NR * (NR + 1) / 2);
+    for (int cI = 0; cI < nfull; ++cI) segment(std::integral_constant<int, 4>{}, cI, scale0);
+    if (nit_last == 2) segment(std::integral_constant<int, 2>{}, nfull, scale0);
+    else if (nit_last == 1) segment(std::integral_constant<int, 1>{}, nfull, scale0);
+    const int nseg = nfull + (nit_last == 1 || nit_last == 2 ? 1 : 0), total = nl * (nseg * (nseg + 1) / 2);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");            // the re-fetched tail stages and the last prefetch
     if (PROF && blockIdx.x == 0 && tid == 0)
         printf("wide prof (block 0, wave 0): stages %d  wait %llu  sub0 %llu  sub1 %llu  sub2 %llu  sub3 %llu  tail %llu  epilogue %llu  (cycles)\n", total,

@@ -32,6 +32,8 @@
 //   firth_w=0        [1]  the one-pass kernel's single-precision first pass at one wavefront per SIMD (firth_fast.hip) instead of two (firth_fast_w.hip)
 //   lmm_limbs=L      [auto] int8 limbs of the LMM contraction;  lmm_tol=X [1e-8] bound above which a variant is contracted with the extra limbs
 //   qf=V             [4]  LMM contraction kernel: 0 = k_lmm_quadform_i8 (two wavefronts per SIMD), 3x = timing ablations
+//   ragged=0         [1]  LMM: the rows behind the last full 128-row tile contracted by the wide kernel itself (a narrow or a full segment) instead of
+//                    k_lmm_ragged_i8 (N mod 128 in 1 .. LMM_RAGGED_MAX)
 //   lanes=n          [3]  lanes of a fixed-effects context (sh_set_lanes overrides)
 //   reader=serial|zlib [par] container decoder of the native reader;  reader_threads=T  its parser workers
 //   wait=spin        [sleep], job=0 / py [1], dma=0 [1], procs=0 [1]   command line (pyseer_amd/__main__.py, input.py): host threads spin on the device; the
@@ -49,7 +51,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)
