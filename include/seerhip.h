@@ -376,6 +376,14 @@ int         sh_burden_fold(sh_ctx *ctx, const uint8_t *present, const uint8_t *m
  *     (their index in the block and their carrier count in kept_idx / kept_count, V entries each, the caller's) or a negative status.
  *     The matrix grows as needed (sh_enet_begin's capacity is the initial one: at least twice the rows, copied device to device); a growth
  *     that fails returns SH_ENOMEM with the matrix as it was.  Forgets the last fit, like append.
+ *   ingest_calls: the same loop for a block of V parsed rows WITH missing calls (the layout sh_vcf_next and sh_burden_fold write: a present
+ *     and a missing row per variant, host pointers; missing may be NULL: no missing calls; skip may be NULL, else skip[v] != 0 drops row v:
+ *     the reader's skip reason).  Over the first n_samples bits c = popcount(present), m = popcount(missing & ~present), t = c + m: the
+ *     reference counts a missing call as a carrier in af (input.py:439-446).  A row is kept iff it is not skipped, min_count <= t <= max_count
+ *     and m <= max_missing_count (an empty interval or max_missing_count < 0 keeps nothing), and is stored by its absences (~present &
+ *     ~missing) when 2 * t > n_samples: the words sh_enet_append(present, missing, flip) stores.  kept_idx / kept_present / kept_missing
+ *     (V entries each, the caller's) take the block index, c and m of the kept rows; growth, SH_ENOMEM and the last fit as for ingest.
+ *     With missing == NULL and skip == NULL it is ingest.
  *   correlations: |cor(row, y)| of enet.py:398-418 for every row, NaN for a row without carriers.  The quantile cut is the caller's.
  *   keep: compact the matrix to rows idx[0 .. n_keep) (ascending or not); get_rows: copy rows idx[] out (host pointer), e.g. the selected
  *     variants for the per-variant engine, so that no input is read twice (enet.py:424 find_enet_selected reads it again).
@@ -409,6 +417,8 @@ typedef struct sh_enet_out {
 int     sh_enet_begin(sh_ctx *ctx, int64_t row_bytes, int64_t capacity);
 int     sh_enet_append(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, const uint8_t *flip, int64_t V);
 int64_t sh_enet_ingest(sh_ctx *ctx, const uint8_t *bits, int64_t V, int32_t min_count, int32_t max_count, int32_t *kept_idx, int32_t *kept_count);
+int64_t sh_enet_ingest_calls(sh_ctx *ctx, const uint8_t *present, const uint8_t *missing, const int32_t *skip, int64_t V, int32_t min_count, int32_t max_count,
+                             int32_t max_missing_count, int32_t *kept_idx, int32_t *kept_present, int32_t *kept_missing);
 int64_t sh_enet_rows(sh_ctx *ctx);
 int     sh_enet_correlations(sh_ctx *ctx, const double *y, double *out_abs_cor);
 /* out[f * rows + j] = sum over the carriers i of row j of vectors[f * n_samples + i] (k_enet_grad, 16 vectors a pass): the pass behind the

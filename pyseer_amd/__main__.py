@@ -10,7 +10,8 @@ tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 --lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 16).
 
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
-reader (--python-reader).  Not supported (out of scope): --wg (enet/rf), BCF, and --gpus / the packed cache with a VCF.
+reader (--python-reader).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
+and --pres and --python-reader line by line.  Not supported (out of scope): --wg rf / blup, BCF, and --gpus / the packed cache with a VCF.
 """
 import argparse
 import os
@@ -221,7 +222,8 @@ def main(argv=None):
             _die('--wg enet runs on one device: --gpus and --packed-part are not available with it\n')
         if (options.load_packed or options.save_packed or options.packed_cache or (options.kmers and len(options.kmers) > 1)) and \
                 (options.python_reader or options.pres or not (options.kmers or options.load_packed)):
-            # (raw blocks and the cache hold k-mer lines, which have no missing calls: --pres, --vcf and --python-reader keep the line-by-line path)
+            # (raw blocks and the cache hold k-mer lines, which have no missing calls: --vcf has its own native route without a cache, --pres and
+            # --python-reader keep the line-by-line path)
             _die('--wg enet reads one variant file through the Python readers: the packed cache and several --kmers files are not available with it\n')
         if options.load_packed and options.save_packed and os.path.realpath(options.load_packed) == os.path.realpath(options.save_packed):
             _die('--save-packed and --load-packed name the same file\n')

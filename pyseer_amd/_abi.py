@@ -109,6 +109,8 @@ SIGNATURES = {
     "sh_enet_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "sh_enet_append": (C.c_int, [C.c_void_p, c_u8p, c_u8p, c_u8p, C.c_int64]),
     "sh_enet_ingest": (C.c_int64, [C.c_void_p, c_u8p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sh_enet_ingest_calls": (C.c_int64, [C.c_void_p, c_u8p, c_u8p, C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sh_enet_rows": (C.c_int64, [C.c_void_p]),
     "sh_enet_correlations": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "sh_enet_carrier_sums": (C.c_int, [C.c_void_p, c_dp, C.c_int, c_dp]),

@@ -62,6 +62,9 @@ hipError_t shk_enet_store(hipStream_t, const uint8_t *, const uint8_t *, const u
 hipError_t shk_enet_gather(hipStream_t, const uint64_t *, const int64_t *, int64_t, int, uint64_t *);
 hipError_t shk_enet_ingest_count(hipStream_t, const uint64_t *, int64_t, int, int, int, int, int32_t *, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t shk_enet_ingest_scatter(hipStream_t, const uint64_t *, int64_t, int, int, const int32_t *, const int32_t *, uint64_t *);
+hipError_t shk_enet_ingest_calls_count(hipStream_t, const uint64_t *, const uint64_t *, const int32_t *, int64_t, int, int, int, int, int, int32_t *, int32_t *, int32_t *,
+                                       int32_t *, int32_t *, int32_t *, int32_t *);
+hipError_t shk_enet_ingest_calls_scatter(hipStream_t, const uint64_t *, const uint64_t *, int64_t, int, int, const int32_t *, const int32_t *, const int32_t *, uint64_t *);
 hipError_t shk_enet_moments(hipStream_t, const uint64_t *, int64_t, int, int, const double *, double, double *);
 hipError_t shk_enet_grad(hipStream_t, const uint64_t *, int64_t, int, const double *, int64_t, int, double *, int64_t);
 size_t shk_enet_cd_lds_bytes(int, int);

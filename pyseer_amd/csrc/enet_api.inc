@@ -8,6 +8,8 @@ struct EnetState {
     uint64_t *d_B = nullptr;
     // sh_enet_ingest: the block as it came from the host, and per row its count and destination, the kept rows' indices and counts, the total
     uint64_t *d_stage = nullptr; int32_t *d_meta = nullptr; int64_t stage_rows = 0;
+    // sh_enet_ingest_calls: the present and the missing block, and per row its two counts, skip flag and destination, the kept rows' figures
+    uint64_t *d_cstage_p = nullptr, *d_cstage_m = nullptr; int32_t *d_cmeta = nullptr; int64_t cstage_rows = 0;
     // the last fit
     int F1 = 0, n_cov = 0, n_lam = 0, N = 0;
     std::vector<std::vector<EnetPoint>> path;                        // [problem][lambda]
@@ -26,7 +28,16 @@ struct DevBuf {                                                      // a device
 static void enet_forget_fit(EnetState *e) { e->n_lam = 0; e->F1 = 0; e->path.clear(); e->eta.clear(); }
 
 // (the staging of the last ingested block is of no use to a fit or a cut: up to 166 MB at N = 5000 go back to the device)
-static void enet_free_stage(EnetState *e) { hipFree(e->d_stage); hipFree(e->d_meta); e->d_stage = nullptr; e->d_meta = nullptr; e->stage_rows = 0; }
+static void enet_free_cstage(EnetState *e)
+{
+    hipFree(e->d_cstage_p); hipFree(e->d_cstage_m); hipFree(e->d_cmeta);
+    e->d_cstage_p = e->d_cstage_m = nullptr; e->d_cmeta = nullptr; e->cstage_rows = 0;
+}
+static void enet_free_stage(EnetState *e)
+{
+    hipFree(e->d_stage); hipFree(e->d_meta); e->d_stage = nullptr; e->d_meta = nullptr; e->stage_rows = 0;
+    enet_free_cstage(e);
+}
 
 static void enet_free(sh_ctx *c)
 {
@@ -122,6 +133,48 @@ int64_t sh_enet_ingest(sh_ctx *c, const uint8_t *bits, int64_t V, int32_t min_co
     HIPCHK(shk_enet_ingest_scatter(c->stream, e->d_stage, V, (int)e->NW, c->N, d_cnt, d_dest, e->d_B + e->P * e->NW));
     HIPCHK(hipMemcpyAsync(kept_idx, d_kidx, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(kept_count, d_kcnt, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    e->P += kept;
+    return kept;
+}
+
+int64_t sh_enet_ingest_calls(sh_ctx *c, const uint8_t *present, const uint8_t *missing, const int32_t *skip, int64_t V, int32_t min_count, int32_t max_count,
+                             int32_t max_missing_count, int32_t *kept_idx, int32_t *kept_present, int32_t *kept_missing)
+{
+    if (!c || !c->enet) return fail(SH_EINVAL, "sh_enet_ingest_calls before sh_enet_begin");
+    EnetState *e = c->enet;
+    if (V < 0 || V > INT32_MAX) return fail(SH_ESHAPE, "sh_enet_ingest_calls: a block holds 0 .. 2^31 - 1 rows");
+    if (V > 0 && (!present || !kept_idx || !kept_present || !kept_missing)) return fail(SH_EINVAL, "sh_enet_ingest_calls: null argument");
+    enet_forget_fit(e);
+    if (V == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (V > e->cstage_rows) {
+        enet_free_cstage(e);
+        if (hipMalloc((void **)&e->d_cstage_p, (size_t)V * e->NW * 8) != hipSuccess || hipMalloc((void **)&e->d_cstage_m, (size_t)V * e->NW * 8) != hipSuccess ||
+            hipMalloc((void **)&e->d_cmeta, ((size_t)7 * V + 1) * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError(); enet_free_cstage(e);
+            return fail(SH_ENOMEM, "sh_enet_ingest_calls: the block does not fit the device");
+        }
+        e->cstage_rows = V;
+    }
+    int32_t *d_cp = e->d_cmeta, *d_cm = d_cp + V, *d_skip = d_cm + V, *d_dest = d_skip + V, *d_kidx = d_dest + V, *d_kp = d_kidx + V, *d_km = d_kp + V, *d_n = d_km + V;
+    const size_t bytes = (size_t)V * e->NW * 8;
+    HIPCHK(hipMemcpyAsync(e->d_cstage_p, present, bytes, hipMemcpyHostToDevice, c->stream));
+    if (missing) HIPCHK(hipMemcpyAsync(e->d_cstage_m, missing, bytes, hipMemcpyHostToDevice, c->stream));
+    if (skip) HIPCHK(hipMemcpyAsync(d_skip, skip, (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const uint64_t *d_miss = missing ? e->d_cstage_m : nullptr;
+    HIPCHK(shk_enet_ingest_calls_count(c->stream, e->d_cstage_p, d_miss, skip ? d_skip : nullptr, V, (int)e->NW, c->N, min_count, max_count, max_missing_count,
+                                       d_cp, d_cm, d_dest, d_kidx, d_kp, d_km, d_n));
+    int32_t kept = 0;
+    HIPCHK(hipMemcpyAsync(&kept, d_n, sizeof(kept), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (kept < 0 || kept > V) return fail(SH_EHIP, "sh_enet_ingest_calls: the scan returned an impossible count");
+    if (kept == 0) return 0;
+    const int rc = enet_reserve(c, e->P + kept); if (rc) return rc;
+    HIPCHK(shk_enet_ingest_calls_scatter(c->stream, e->d_cstage_p, d_miss, V, (int)e->NW, c->N, d_cp, d_cm, d_dest, e->d_B + e->P * e->NW));
+    HIPCHK(hipMemcpyAsync(kept_idx, d_kidx, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(kept_present, d_kp, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(kept_missing, d_km, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     e->P += kept;
     return kept;

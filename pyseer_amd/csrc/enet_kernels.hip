@@ -4,6 +4,7 @@
 // fold are the SAME problem with different sample weights (a held-out sample has weight 0), so they share B and differ in N-vectors only.
 //   k_enet_store        minor-allele coding of load_all_vars (enet.py:95-106) while the rows are put in place
 //   k_enet_ingest_*     the same rule and coding applied ON the device to a block of parsed k-mer rows: count, ordered scan, compacted store
+//   k_enet_ingest_calls_*  the same for rows with missing calls (VCF records, burden regions): a present and a missing row, a skip flag
 //   k_enet_moments      |correlation| of every row with the phenotype (enet.py:379-421)
 //   k_enet_grad         G[f][j] = sum over the carriers i of row j of V[f][i], up to 16 vectors per pass, fp64: weighted means, training
 //                       counts, lambda_max, the strong rule and the KKT check over ALL rows
@@ -135,6 +136,80 @@ __global__ void k_enet_ingest_scatter(const uint64_t *__restrict__ rows, int64_t
     const uint64_t *row = rows + v * NW;
     uint64_t *out = dst + (int64_t)d * NW;
     for (int wd = lane; wd < NW; wd += 64) { const uint64_t b = row[wd]; out[wd] = (flip ? ~b : b) & enet_valid_bits(wd, N); }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// k_enet_ingest_calls_*: the same for rows WITH missing calls (VCF records, burden regions): a present and a missing row per variant, and
+// the reader's skip flag.  c = present, m = missing and not present (a sample set in both rows is present, as in k_enet_store), both over
+// the first N bits; the reference counts a missing call as a carrier in af (input.py:439-446), so the AF interval is on t = c + m and the
+// missing rule on m alone.
+// one wavefront per row, two popcounts per word; miss == NULL: no missing calls
+__global__ void k_enet_ingest_calls_count(const uint64_t *__restrict__ pres, const uint64_t *__restrict__ miss, int64_t V, int NW, int N,
+                                          int32_t *__restrict__ cnt_p, int32_t *__restrict__ cnt_m)
+{
+    const int64_t v = (int64_t)blockIdx.x * ENET_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= V) return;
+    const uint64_t *rp = pres + v * NW, *rm = miss ? miss + v * NW : nullptr;
+    int c = 0, m = 0;
+    for (int wd = lane; wd < NW; wd += 64) {
+        const uint64_t valid = enet_valid_bits(wd, N), b = rp[wd];
+        c += __popcll(b & valid);
+        if (rm) m += __popcll(rm[wd] & ~b & valid);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { c += __shfl_down(c, o, 64); m += __shfl_down(m, o, 64); }
+    if (lane == 0) { cnt_p[v] = c; cnt_m[v] = m; }
+}
+
+// the ordered scan of k_enet_ingest_scan with the three-part predicate: not skipped, lo <= c + m <= hi, m <= mm (mm < 0 keeps nothing)
+__global__ __launch_bounds__(ENET_SCAN_TPB) void k_enet_ingest_calls_scan(const int32_t *__restrict__ cnt_p, const int32_t *__restrict__ cnt_m,
+                                                                          const int32_t *__restrict__ skip, int64_t V, int lo, int hi, int mm,
+                                                                          int32_t *__restrict__ dest, int32_t *__restrict__ kept_idx,
+                                                                          int32_t *__restrict__ kept_p, int32_t *__restrict__ kept_m, int32_t *__restrict__ n_kept)
+{
+    __shared__ int wsum[ENET_SCAN_TPB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < V; base += ENET_SCAN_TPB) {
+        const int64_t v = base + tid;
+        const int c = v < V ? cnt_p[v] : 0, m = v < V ? cnt_m[v] : 0;
+        const int t = c + m;
+        const bool keep = v < V && !(skip && skip[v] != 0) && t >= lo && t <= hi && m <= mm;
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) wsum[wv] = __popcll(b);
+        __syncthreads();
+        int before = __popcll(b & ((1ull << lane) - 1ull)), total = 0;
+        for (int w = 0; w < ENET_SCAN_TPB / 64; ++w) { const int s = wsum[w]; if (w < wv) before += s; total += s; }
+        if (v < V) {
+            dest[v] = keep ? carry + before : -1;
+            if (keep) { kept_idx[carry + before] = (int32_t)v; kept_p[carry + before] = c; kept_m[carry + before] = m; }
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) *n_kept = carry;
+}
+
+// one wavefront per row: both rows of a kept row are read; 2 (c + m) > N stores the absences, a missing call being 0 in either coding
+// (~present & ~missing), padding bits 0: the words k_enet_store writes for (present, missing, flip)
+__global__ void k_enet_ingest_calls_scatter(const uint64_t *__restrict__ pres, const uint64_t *__restrict__ miss, int64_t V, int NW, int N,
+                                            const int32_t *__restrict__ cnt_p, const int32_t *__restrict__ cnt_m, const int32_t *__restrict__ dest,
+                                            uint64_t *__restrict__ dst)
+{
+    const int64_t v = (int64_t)blockIdx.x * ENET_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= V) return;
+    const int d = dest[v];
+    if (d < 0) return;
+    const bool flip = 2 * ((int64_t)cnt_p[v] + (int64_t)cnt_m[v]) > (int64_t)N;
+    const uint64_t *rp = pres + v * NW, *rm = miss ? miss + v * NW : nullptr;
+    uint64_t *out = dst + (int64_t)d * NW;
+    for (int wd = lane; wd < NW; wd += 64) {
+        uint64_t b = rp[wd];
+        if (flip) { b = ~b; if (rm) b &= ~rm[wd]; }
+        out[wd] = b & enet_valid_bits(wd, N);
+    }
 }
 
 // one wavefront per row: carrier count and carrier sum of yc = y - mean(y);  cor = |ab / sqrt(sum a^2 sum b^2)| with a = k - mean(k)
@@ -438,6 +513,23 @@ hipError_t shk_enet_ingest_scatter(hipStream_t st, const uint64_t *rows, int64_t
 {
     if (V <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_enet_ingest_scatter, dim3((unsigned)((V + ENET_WAVES - 1) / ENET_WAVES)), dim3(ENET_TPB), 0, st, rows, V, NW, N, cnt, dest, dst);
+    return hipGetLastError();
+}
+// the same two steps for rows with missing calls (miss and skip may be NULL)
+hipError_t shk_enet_ingest_calls_count(hipStream_t st, const uint64_t *pres, const uint64_t *miss, const int32_t *skip, int64_t V, int NW, int N, int lo, int hi,
+                                       int mm, int32_t *cnt_p, int32_t *cnt_m, int32_t *dest, int32_t *kept_idx, int32_t *kept_p, int32_t *kept_m, int32_t *n_kept)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_enet_ingest_calls_count, dim3((unsigned)((V + ENET_WAVES - 1) / ENET_WAVES)), dim3(ENET_TPB), 0, st, pres, miss, V, NW, N, cnt_p, cnt_m);
+    hipLaunchKernelGGL(k_enet_ingest_calls_scan, dim3(1), dim3(ENET_SCAN_TPB), 0, st, cnt_p, cnt_m, skip, V, lo, hi, mm, dest, kept_idx, kept_p, kept_m, n_kept);
+    return hipGetLastError();
+}
+hipError_t shk_enet_ingest_calls_scatter(hipStream_t st, const uint64_t *pres, const uint64_t *miss, int64_t V, int NW, int N, const int32_t *cnt_p,
+                                         const int32_t *cnt_m, const int32_t *dest, uint64_t *dst)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_enet_ingest_calls_scatter, dim3((unsigned)((V + ENET_WAVES - 1) / ENET_WAVES)), dim3(ENET_TPB), 0, st, pres, miss, V, NW, N, cnt_p, cnt_m,
+                       dest, dst);
     return hipGetLastError();
 }
 hipError_t shk_enet_moments(hipStream_t st, const uint64_t *B, int64_t P, int NW, int N, const double *yc, double sum_b2, double *out)

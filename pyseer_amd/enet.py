@@ -113,6 +113,32 @@ class EnetMatrix(object):
             _abi.check(int(kept))
         return idx[:kept], cnt[:kept]
 
+    def ingest_calls(self, present, missing, skip, lo, hi, mm):
+        """A block of parsed rows with missing calls (an input.CallBlock's present / missing rows; missing and skip may be None): the rows
+        that are not skipped, with lo <= present + missing <= hi and missing <= mm (call_bounds), are appended in their order, coded by the
+        minor allele, on the device (k_enet_ingest_calls_*).  Returns (index in the block, present count, missing count) of the kept rows."""
+        def rows_of(a, V):
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.shape != (V, self.row_bytes) or not a.flags.c_contiguous:
+                a = self._u8(a, V)
+            return a
+        V = np.asarray(present).shape[0]
+        present = rows_of(present, V)
+        missing = None if missing is None else rows_of(missing, V)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            if skip.shape != (V,):
+                raise ValueError("skip must have one entry per row")
+        idx, n_p, n_m = np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        kept = self._lib.sh_enet_ingest_calls(self._h, C.cast(present.ctypes.data, _abi.c_u8p),
+                                              None if missing is None else C.cast(missing.ctypes.data, _abi.c_u8p),
+                                              None if skip is None else skip.ctypes.data_as(i32), V, int(lo), int(hi), int(mm),
+                                              idx.ctypes.data_as(i32), n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32))
+        if kept < 0:
+            _abi.check(int(kept))
+        return idx[:kept], n_p[:kept], n_m[:kept]
+
     def correlations(self, y):
         if self.rows < 1:
             raise ValueError("No variants passed filters")
@@ -193,6 +219,8 @@ class EnetMatrix(object):
 # the command line's --wg enet (pyseer/__main__.py:598-712 over pyseer/enet.py)
 # ---------------------------------------------------------------------------------------------------------------
 TEST_BETAS = None          # test-only hook: a function (n_cov, var_indices) -> betas[1 + n_cov + P] used instead of the fit's
+LAST_LOAD_ROUTE = None     # how the last run_cli loaded its variants: "calls" (native VCF reader, sh_enet_ingest_calls), "blocks" (raw k-mer
+                           # blocks, sh_enet_ingest) or "lines" (read_variant): the three print the same, so a test needs this to tell them apart
 
 
 def load_all_vars(engine, var_type, p, burden, burden_regions, infile, all_strains, sample_order, min_af, max_af, max_missing, uncompressed):
@@ -275,6 +303,77 @@ def load_all_vars_blocks(engine, p, blocks, min_af, max_af, max_missing, capacit
     return M, np.concatenate(var_idx), loaded, np.concatenate(blobs), off, np.concatenate(counts)
 
 
+def call_bounds(n, min_af, max_af, max_missing):
+    """load_all_vars' rule for a line with missing calls as bounds on counts: (lo, hi, mm) with the line kept iff lo <= t <= hi and m <= mm,
+    t = present + missing calls (read_variant counts a missing call as a carrier in af), m = missing calls.  The reference's own expressions
+    (enet.py:95: `af > min_af and af < max_af and missing < max_missing`, af = float(t) / n, missing = float(m) / n) are evaluated at every
+    count 0 .. n; both are monotone in the count.  (1, 0) for the interval, -1 for mm, when nothing passes."""
+    af = np.array([float(t) / n for t in range(n + 1)])
+    keep = np.nonzero((af > min_af) & (af < max_af))[0]
+    miss = np.nonzero(np.array([float(m) / n for m in range(n + 1)]) < max_missing)[0]
+    lo, hi = (int(keep[0]), int(keep[-1])) if keep.size else (1, 0)
+    return lo, hi, (int(miss[-1]) if miss.size else -1)
+
+
+class KeptCalls(object):
+    """What load_all_vars_calls keeps on the host per row of the matrix: the name (blob / off), t = present + missing calls, the packed
+    missing row of a row that has a missing call (row_bytes each: a row stored by its absences cannot be complemented back without it) and
+    the text read_variant writes while it parses the variant.  take(idx) cuts all of them together."""
+
+    def __init__(self, blob, off, counts, has_missing, missing_rows, messages):
+        self.blob, self.off, self.counts, self.has_missing, self.missing_rows, self.messages = blob, off, counts, has_missing, missing_rows, messages
+
+    def take(self, idx):
+        idx = np.asarray(idx, dtype=np.int64)
+        blob, off = _take_names(self.blob, self.off, idx)
+        at = np.cumsum(self.has_missing) - 1                          # row of missing_rows of every row that has one
+        has = self.has_missing[idx]
+        return KeptCalls(blob, off, self.counts[idx], has, self.missing_rows[at[idx][has]], self.messages[idx])
+
+    def missing_list(self):
+        """per row its packed missing row, None where it has no missing call"""
+        at = np.cumsum(self.has_missing) - 1
+        return [self.missing_rows[at[i]] if self.has_missing[i] else None for i in range(self.has_missing.size)]
+
+
+def load_all_vars_calls(engine, p, call_blocks, min_af, max_af, max_missing, err, capacity=1 << 16):
+    """load_all_vars for VCF input over the call-block stream of the native reader (input.CallBlock: every variant, in order, with its
+    missing calls): per block the variants' messages go to `err` in order, as read_variant writes them on the first pass ("No observations
+    of X in selected samples" for every parsed variant nobody carries), and sh_enet_ingest_calls keeps, codes and appends the rows.
+    Returns (EnetMatrix, var_indices, number of variants read, KeptCalls); var_indices count every variant read, skipped records included."""
+    n = len(p)
+    lo, hi, mm = call_bounds(n, min_af, max_af, max_missing)
+    M = EnetMatrix(engine, capacity)
+    var_idx, blobs, lens, counts, has, mrows, msgs, loaded = [], [], [], [], [], [], [], 0
+    try:
+        for blk in call_blocks:
+            empty = (np.asarray(blk.skip) == 0) & (np.asarray(blk.n_present) + np.asarray(blk.n_missing) == 0)
+            messages = blk.messages
+            said = set(np.nonzero(empty)[0].tolist())
+            said.update(i for i, t in enumerate(messages) if t)
+            for i in sorted(said):
+                err.write(messages[i])
+                if empty[i]:
+                    err.write("No observations of " + bytes(blk.blob[blk.off[i]:blk.off[i + 1]]).decode() + " in selected samples\n")
+            idx, n_p, n_m = M.ingest_calls(blk.present, blk.missing, blk.skip, lo, hi, mm)
+            if idx.size:
+                b, o = _take_names(blk.blob, blk.off, idx)
+                var_idx.append(idx.astype(np.int64) + loaded); blobs.append(b); lens.append(np.diff(o)); counts.append(n_p + n_m)
+                has.append(n_m > 0); mrows.append(np.asarray(blk.missing)[idx[n_m > 0]])
+                msgs.append(np.array([messages[i] for i in idx], dtype=object))
+            loaded += len(blk)
+    except BaseException:
+        M.close()
+        raise
+    if not var_idx:
+        M.close()
+        raise ValueError("No variants passed filters")
+    off = np.zeros(sum(x.size for x in lens) + 1, dtype=np.int64)
+    np.cumsum(np.concatenate(lens), out=off[1:])
+    kept = KeptCalls(np.concatenate(blobs), off, np.concatenate(counts), np.concatenate(has), np.concatenate(mrows), np.concatenate(msgs))
+    return M, np.concatenate(var_idx), loaded, kept
+
+
 def _r2(y_true, y_pred):
     """sklearn.metrics.r2_score for one output."""
     ss_res, ss_tot = np.sum((y_true - y_pred) ** 2), np.sum((y_true - np.mean(y_true)) ** 2)
@@ -347,10 +446,14 @@ def _enet_row(var_name, k, af, kstrains, nkstrains, beta, p, c, fit_seer, contin
     return Enet(var_name, af, pval, adj_pval, beta, max_lineage, kstrains, nkstrains, notes)
 
 
-def selected_from_rows(enet_betas, rows, names, counts, p, c, fit_seer, continuous, find_lineage, lin, err):
+def selected_from_rows(enet_betas, rows, names, counts, p, c, fit_seer, continuous, find_lineage, lin, err, missing_rows=None, messages=None):
     """find_enet_selected without a second pass over the input: `rows` are the matrix's rows of the columns with a non-zero slope
     (EnetMatrix.get_rows, fetched before the matrix was closed), in stream order; names = (blob, offsets) and counts are theirs.  A row
-    stored by its absences (2 * count > n) is complemented back over the n samples."""
+    stored by its absences (2 * count > n) is complemented back over the n samples.
+    VCF input (load_all_vars_calls): counts are present + missing calls; missing_rows[i] is the packed missing row of row i, or None where
+    it has no missing call -- a missing call is 0 in either stored coding, so present = ~stored & ~missing when flipped --, and messages[i]
+    the text the reference's second pass writes again when it parses the selected line (a burden line's "Multiple alleles" and "Could not
+    parse region").  A missing call is a carrier in the sample lists and in af, and NaN in k, as read_variant has it."""
     from .input import strains_from_bits
     n = len(p)
     samples = [str(x) for x in p.index]
@@ -361,13 +464,21 @@ def selected_from_rows(enet_betas, rows, names, counts, p, c, fit_seer, continuo
     valid = np.packbits(tail, bitorder="little")
     for i, beta in enumerate(enet_betas):
         row = rows[i]
+        miss = None if missing_rows is None else missing_rows[i]
+        if messages is not None:
+            err.write(messages[i])
         if 2 * int(counts[i]) > n:
             row = ~row & valid
+            if miss is not None:
+                row = row & ~miss
         var_name = bytes(blob[off[i]:off[i + 1]]).decode()
-        kstrains, nkstrains = strains_from_bits(row, order, samples)
+        kstrains, nkstrains = strains_from_bits(row if miss is None else (row | (miss & valid)), order, samples)
         if len(kstrains) == 0:                                        # (read_variant says so whenever it parses such a line)
             err.write("No observations of " + var_name + " in selected samples\n")
         k = np.unpackbits(row, bitorder="little")[:n].astype(np.int64)
+        if miss is not None:
+            k = k.astype(float)
+            k[np.unpackbits(miss, bitorder="little")[:n].astype(bool)] = np.nan
         yield _enet_row(var_name, k, float(int(counts[i])) / n, kstrains, nkstrains, beta, p, c, fit_seer, continuous, find_lineage, lin)
 
 
@@ -381,15 +492,19 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
     kmers = list(options.kmers) if options.kmers else []
     var_type, var_file = ("kmers", kmers[0]) if kmers else (("vcf", options.vcf) if options.vcf else ("Rtab", options.pres))
     all_strains = set(p.index)
-    # k-mers come as raw blocks from the native reader or the packed cache and are filtered, coded and stored on the device
-    # (load_all_vars_blocks); --python-reader, --vcf and --pres go line by line through read_variant (load_all_vars)
+    # k-mers come as raw blocks from the native reader or the packed cache (load_all_vars_blocks), --vcf (with or without --burden) as call
+    # blocks from the native VCF reader (load_all_vars_calls): both are filtered, coded and stored on the device and read once;
+    # --python-reader and --pres go line by line through read_variant (load_all_vars)
+    global LAST_LOAD_ROUTE
     native = bool(options.load_packed) or (var_type == "kmers" and not options.python_reader)
+    calls = var_type == "vcf" and not options.python_reader and not options.load_packed
+    LAST_LOAD_ROUTE = "blocks" if native else ("calls" if calls else "lines")
 
     def reopen():
         regions = collections.deque([]) if options.burden else None
         infile, sample_order = open_variant_file(var_type, var_file, options.burden, regions, options.uncompressed)
         return infile, sample_order, regions
-    names = counts = None
+    names = counts = kept = None
     if native:
         from .input import open_kmer_block_stream
         blocks, cache_out = open_kmer_block_stream(options, p, kmers, max(options.block_size, 1 << 18))
@@ -405,6 +520,15 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
         names = (blob, off)
         if cache_out is not None:
             cache_out.close()                                         # (the whole input has been read: the cache is complete)
+    elif calls:
+        from .input import iter_call_blocks_vcf_native, load_burden
+        regions = None
+        if options.burden:
+            regions = []
+            load_burden(options.burden, regions)
+        # (2^14 records a block: 2 x 10 MB of rows at N = 5000, and the reader's launches and the three of the ingest are spread over many records)
+        blocks = iter_call_blocks_vcf_native(p, var_file, engine, max(options.block_size, 1 << 14), burden_regions=regions)
+        M, var_indices, loaded, kept = load_all_vars_calls(engine, p, blocks, options.min_af, options.max_af, options.max_missing, err)
     else:
         infile, sample_order, regions = reopen()
         M, var_indices, loaded = load_all_vars(engine, var_type, p, bool(options.burden), regions, infile, all_strains, sample_order,
@@ -420,6 +544,8 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
         var_indices = var_indices[keep]
         if native:
             names, counts = _take_names(names[0], names[1], keep), counts[keep]
+        if calls:
+            kept = kept.take(keep)
     tested = len(var_indices)
     prefilter = loaded - tested
     weights, fold_ids = np.ones(len(p)), None
@@ -471,9 +597,16 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
         sel_rows = M.get_rows(sel)
         selected = selected_from_rows(betas[cov.shape[1] + 1:][sel], sel_rows, _take_names(names[0], names[1], sel), counts[sel], p, cov, fit_seer,
                                       options.continuous, bool(options.lineage), lineage_clusters, err)
+    if calls:
+        sel = np.nonzero(betas[cov.shape[1] + 1:])[0]
+        sel_rows = M.get_rows(sel)
+        kept = kept.take(sel)
+        selected = selected_from_rows(betas[cov.shape[1] + 1:][sel], sel_rows, (kept.blob, kept.off), kept.counts, p, cov, fit_seer,
+                                      options.continuous, bool(options.lineage), lineage_clusters, err,
+                                      missing_rows=kept.missing_list(), messages=kept.messages)
     M.close()
     engine.close()
-    if not native:
+    if not (native or calls):
         infile, sample_order, regions = reopen()
         selected = find_enet_selected(betas, var_indices, p, cov, var_type, fit_seer, bool(options.burden), regions, infile, all_strains,
                                       sample_order, options.continuous, bool(options.lineage), lineage_clusters, options.uncompressed)

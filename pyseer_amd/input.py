@@ -711,25 +711,43 @@ def _merged_intervals(regions):
     return out
 
 
-def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, burden_regions=None):
-    """The PackedBlock stream of iter_packed_blocks(p, 'vcf', ...) fed by the native reader.  burden_regions: the (name, [region, ...]) list
-    load_burden fills -- one variant per entry: the file is read once, the rows of the records that lie in any region are kept, and
-    k_burden_fold (sh_burden_fold) combines each variant's records on the device."""
-    samples = [str(x) for x in p.index]
-    order = sorted(range(len(samples)), key=lambda i: samples[i])
-    n = len(samples)
-    reader = NativeVcfReader(path, samples, engine, block_size)
+class CallBlock(object):
+    """One block of variants with missing calls as the native VCF reader (or k_burden_fold over its rows) delivers them, every variant in
+    input order and BEFORE any AF window: names (blob / off, `names` decodes them), the reader's skip reason, the packed present / missing
+    rows with their counts, and per variant the text read_variant writes to stderr while it applies its records ("Multiple alleles at ...
+    Skipping", "Could not parse region None"; "" for most)."""
+    __slots__ = ("blob", "off", "skip", "present", "missing", "n_present", "n_missing", "messages", "_names")
 
-    def multi_message(contig, pos):
-        return "Multiple alleles at %s_%d. Skipping\n" % (contig, pos)
+    def __init__(self, blob, off, skip, present, missing, n_present, n_missing, messages):
+        self.blob, self.off, self.skip, self.present, self.missing = blob, off, skip, present, missing
+        self.n_present, self.n_missing, self.messages, self._names = n_present, n_missing, messages, None
 
+    def __len__(self):
+        return int(self.skip.shape[0])
+
+    @property
+    def names(self):
+        if self._names is None:
+            blob, off = self.blob, self.off
+            self._names = [blob[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)]
+        return self._names
+
+
+def _multi_message(contig, pos):
+    return "Multiple alleles at %s_%d. Skipping\n" % (contig, pos)
+
+
+def _vcf_call_blocks(reader, engine, block_size, burden_regions=None):
+    """The CallBlock stream behind iter_packed_blocks_vcf_native and iter_call_blocks_vcf_native: one variant per record, or, with
+    burden_regions (the (name, [region, ...]) list load_burden fills), one per entry: the file is read once, the rows of the records that lie
+    in any region are kept, and k_burden_fold (sh_burden_fold) combines each variant's records on the device."""
     def plain():
         for rb in reader.raw_blocks():
-            blob, off = rb["blob"], rb["off"]
-            names = [blob[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)]
-            msgs = [multi_message(reader.contig(rb["contig"][i]), int(rb["pos"][i])) if rb["skip"][i] == VCF_MULTI else "" for i in range(len(names))]
-            yield _vcf_packed_block(n, samples, order, names, rb["skip"], rb["present"], rb["missing"], rb["n_present"], rb["n_missing"],
-                                    min_af, max_af, max_missing, want_patterns, msgs)
+            nv = rb["skip"].shape[0]
+            msgs = [""] * nv
+            for i in np.nonzero(rb["skip"] == VCF_MULTI)[0]:
+                msgs[i] = _multi_message(reader.contig(rb["contig"][i]), int(rb["pos"][i]))
+            yield CallBlock(rb["blob"], rb["off"], rb["skip"], rb["present"], rb["missing"], rb["n_present"], rb["n_missing"], msgs)
 
     def burden():
         import ctypes as C
@@ -785,7 +803,7 @@ def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, 
                     cand = np.sort(cand[kb[cand] > start])                   # file order
                     for rec in cand:
                         if ksk[rec] == VCF_MULTI:
-                            msg += multi_message(contig, int(ka[rec]) + 1)
+                            msg += _multi_message(contig, int(ka[rec]) + 1)
                         if ksk[rec] == VCF_KEPT:
                             csr_idx.append(int(rec))
                 msgs.append(msg)
@@ -799,12 +817,38 @@ def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, 
             _abi.check(lib.sh_burden_fold(engine._h, kp.ctypes.data_as(_abi.c_u8p), km.ctypes.data_as(_abi.c_u8p), rb_, kp.shape[0], off_a.ctypes.data_as(i64),
                                           idx_a.ctypes.data_as(i32), nvar, out_p.ctypes.data_as(_abi.c_u8p), out_m.ctypes.data_as(_abi.c_u8p),
                                           n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32)))
-            yield _vcf_packed_block(n, samples, order, [variants[v][0] for v in chunk], np.zeros(nvar, dtype=np.int32), out_p, out_m, n_p, n_m,
-                                    min_af, max_af, max_missing, want_patterns, msgs)
-
-    try:
-        for blk in (burden() if burden_regions is not None else plain()):
+            enc = [variants[v][0].encode() for v in chunk]
+            off_n = np.zeros(nvar + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in enc], out=off_n[1:])
+            blk = CallBlock(b"".join(enc), off_n, np.zeros(nvar, dtype=np.int32), out_p, out_m, n_p, n_m, msgs)
+            blk._names = [variants[v][0] for v in chunk]
             yield blk
+
+    return burden() if burden_regions is not None else plain()
+
+
+def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, burden_regions=None):
+    """The PackedBlock stream of iter_packed_blocks(p, 'vcf', ...) fed by the native reader (_vcf_call_blocks; burden_regions: one variant per
+    entry of the (name, [region, ...]) list load_burden fills)."""
+    samples = [str(x) for x in p.index]
+    order = sorted(range(len(samples)), key=lambda i: samples[i])
+    n = len(samples)
+    reader = NativeVcfReader(path, samples, engine, block_size)
+    try:
+        for cb in _vcf_call_blocks(reader, engine, block_size, burden_regions):
+            yield _vcf_packed_block(n, samples, order, cb.names, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing,
+                                    min_af, max_af, max_missing, want_patterns, cb.messages)
+    finally:
+        reader.close()
+
+
+def iter_call_blocks_vcf_native(p, path, engine, block_size, burden_regions=None):
+    """The CallBlock stream of a VCF for the whole-genome models (enet.load_all_vars_calls): every record in input order, or one variant per
+    line of the regions file, before any AF window -- the filter, the coding and the storing are the device's (sh_enet_ingest_calls)."""
+    reader = NativeVcfReader(path, [str(x) for x in p.index], engine, block_size)
+    try:
+        for cb in _vcf_call_blocks(reader, engine, block_size, burden_regions):
+            yield cb
     finally:
         reader.close()
 

@@ -23,16 +23,20 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_MEASURED, HBM_SPEC = 6.29e12, 8.0e12          # bytes/s: float4 copy measured, and the specification
 
 
-def make_file(d, gb):
+def make_file(d, gb, records=None):
+    """gen.vcf.gz (BGZF) of at least `gb` GB of text -- or, with `records`, of at least that many records --, first.vcf (its first 2000 records
+    as plain text) and meta.json under d; (path, meta)."""
     from _vcf_text import bgzf_bytes, generated_vcf
     os.makedirs(d, exist_ok=True)
     path, meta = os.path.join(d, "gen.vcf.gz"), os.path.join(d, "meta.json")
+    if records is not None:
+        gb = "%d records" % records
     if os.path.exists(path) and os.path.exists(meta) and json.load(open(meta))["gb"] == gb:
         return path, json.load(open(meta))
     text, pheno, cols = generated_vcf(n_pheno=5000, n_cols=5200, n_records=2000, seed=7, missing=0.03)
     head_end = text.index(b"\n", text.index(b"#CHROM")) + 1
     body = text[head_end:]
-    tiles = max(1, int(-(-gb * 1e9 // len(body))))
+    tiles = max(1, -(-records // 2000)) if records is not None else max(1, int(-(-gb * 1e9 // len(body))))
     with open(path, "wb") as f:
         f.write(bgzf_bytes(text[:head_end], level=1)[:-28])
         comp = bgzf_bytes(body, level=1)[:-28]                   # (without the end-of-file member)

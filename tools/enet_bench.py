@@ -12,7 +12,17 @@ enet.load_all_vars, the line-by-line path) and reports the process's peak reside
 
     python tools/enet_bench.py --ingest --variants 1048576 --samples 5000
     python tools/enet_bench.py --write-kmers kmers.gz --variants 100000 --samples 5000          # synthetic text + kmers.gz.pheno
-    python tools/enet_bench.py --load-kmers kmers.gz --pheno kmers.gz.pheno [--python-reader]"""
+    python tools/enet_bench.py --load-kmers kmers.gz --pheno kmers.gz.pheno [--python-reader]
+
+--load-vcf FILE times the same stage from a VCF: the native reader alone (sh_vcf_stats), enet.load_all_vars_calls (the command line's route
+for --vcf), and sh_enet_ingest_calls alone on blocks of the file held in host memory; --python-reader: enet.load_all_vars line by line, on
+the whole FILE, so give it a prefix.  --write-vcf DIR generates the input from a seed (tools/bench_vcf_reader.py's generator: N = 5000
+phenotyped samples among 5200 columns, 3 % missing calls): DIR/gen.vcf.gz of --variants records (BGZF), DIR/first.vcf (its first 2000
+records, plain text) and DIR/gen.pheno.
+
+    python tools/enet_bench.py --write-vcf DIR --variants 200000
+    python tools/enet_bench.py --load-vcf DIR/gen.vcf.gz --pheno DIR/gen.pheno
+    python tools/enet_bench.py --load-vcf DIR/first.vcf --pheno DIR/gen.pheno --python-reader"""
 import argparse
 import json
 import os
@@ -158,12 +168,99 @@ def load_kmers_stage(o):
     e.close()
 
 
+def write_vcf(o):
+    """--write-vcf DIR: the generated call set of tools/bench_vcf_reader.py with --variants records, and DIR/gen.pheno for its 5000 samples."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from bench_vcf_reader import make_file
+    path, meta = make_file(o.write_vcf, None, records=o.variants)
+    rng = np.random.default_rng(7)
+    with open(os.path.join(o.write_vcf, "gen.pheno"), "w") as f:
+        f.write("samples\tbinary\n" + "".join("%s\t%d\n" % (s, b) for s, b in zip(meta["samples"], rng.integers(0, 2, len(meta["samples"])))))
+    print(json.dumps(dict(what="generated VCF", path=path, records=meta["records"], text_GB=meta["text_bytes"] / 1e9, file_MB=meta["file_bytes"] / 1e6)), flush=True)
+
+
+def load_vcf_stage(o):
+    from pyseer_amd.engine import Engine
+    from pyseer_amd.enet import EnetMatrix, call_bounds, load_all_vars, load_all_vars_calls
+    from pyseer_amd.input import NativeVcfReader, iter_call_blocks_vcf_native, load_phenotypes, open_variant_file
+    p = load_phenotypes(o.pheno, None)
+    n, B = len(p), o.vcf_block
+    e = Engine(n)
+    devnull = open(os.devnull, "w")
+    if o.python_reader:
+        import contextlib
+        t = time.perf_counter()
+        infile, order = open_variant_file("vcf", o.load_vcf)
+        with contextlib.redirect_stderr(devnull):
+            M, vi, loaded = load_all_vars(e, "vcf", p, False, None, infile, set(p.index), order, 0.01, 0.99, 0.05, False)
+        dt = time.perf_counter() - t
+        print(json.dumps(dict(what="load stage from a VCF, load_all_vars (--python-reader)", records=int(loaded), kept=int(M.rows), samples=n, seconds=dt,
+                              records_per_s=loaded / dt, peak_rss_mb=peak_rss_mb())), flush=True)
+        M.close()
+        e.close()
+        return
+    # the reader alone, twice (the first pass also pays the page cache and the pinned slabs); the blocks of the first --ingest-records stay
+    held, dt_reader = [], 0.0
+    for rep in range(2):
+        r = NativeVcfReader(o.load_vcf, [str(x) for x in p.index], e, B)
+        t = time.perf_counter(); nrec = 0; held = []
+        for rb in r.raw_blocks():
+            if nrec < o.ingest_records:
+                held.append((rb["present"], rb["missing"], rb["skip"]))
+            nrec += rb["skip"].shape[0]
+        dt_reader = time.perf_counter() - t
+        st = r.stats()
+        r.close()
+        print(json.dumps(dict(what="native VCF reader alone, pass %d" % (rep + 1), records=nrec, samples=n, block=B, seconds=dt_reader, records_per_s=nrec / dt_reader,
+                              sample_bytes=st["sample_bytes"], launches=st["launches"])), flush=True)
+    ts = []
+    for rep in range(o.repeats + 1):
+        t = time.perf_counter()
+        M, vi, loaded, kept = load_all_vars_calls(e, p, iter_call_blocks_vcf_native(p, o.load_vcf, e, B), 0.01, 0.99, 0.05, devnull)
+        dt = time.perf_counter() - t
+        rows, with_missing = int(M.rows), int(kept.has_missing.sum())
+        if rep:
+            ts.append(dt)
+        if rep < o.repeats:
+            M.close()
+    med = float(np.median(ts))
+    t = time.perf_counter(); M.correlations(p.values.astype(float)); dc = time.perf_counter() - t
+    M.close()
+    print(json.dumps(dict(what="load stage from a VCF, native reader + load_all_vars_calls", records=int(loaded), kept=rows, kept_with_missing=with_missing,
+                          samples=n, block=B, records_per_s=loaded / med, reader_alone_share=dt_reader / med, correlations_s=dc,
+                          missing_rows_held_mb=with_missing * M.row_bytes / 1e6, peak_rss_mb=peak_rss_mb(), **stats(ts))), flush=True)
+    # sh_enet_ingest_calls alone: the held blocks from host memory, the matrix's capacity reserved
+    lo, hi, mm = call_bounds(n, 0.01, 0.99, 0.05)
+    nheld = sum(b[2].shape[0] for b in held)
+    ts = []
+    for rep in range(o.repeats + 1):
+        M = EnetMatrix(e, nheld)
+        t = time.perf_counter()
+        for pres, miss, skip in held:
+            M.ingest_calls(pres, miss, skip, lo, hi, mm)
+        dt = time.perf_counter() - t
+        rows = int(M.rows)
+        M.close()
+        if rep:
+            ts.append(dt)
+    med = float(np.median(ts))
+    nbytes = 2 * nheld * held[0][0].shape[1]
+    print(json.dumps(dict(what="sh_enet_ingest_calls alone, %d-record blocks of host memory, capacity reserved (host clock around the synchronous calls)" % B,
+                          records=nheld, kept=rows, samples=n, bytes=nbytes, records_per_s=nheld / med, gb_per_s=nbytes / med / 1e9, **stats(ts))), flush=True)
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ingest", action="store_true", help="the load path: sh_enet_ingest alone and from a packed cache")
     ap.add_argument("--load-kmers", default=None, help="time the load stage from this gzipped k-mer file (needs --pheno)")
     ap.add_argument("--pheno", default=None)
     ap.add_argument("--write-kmers", default=None, help="write --variants lines of synthetic gzipped k-mer text (and FILE.pheno) and stop: no device needed")
+    ap.add_argument("--load-vcf", default=None, help="time the load stage from this VCF (needs --pheno)")
+    ap.add_argument("--write-vcf", default=None, help="write DIR/gen.vcf.gz of --variants generated records, DIR/first.vcf and DIR/gen.pheno and stop: no device needed")
+    ap.add_argument("--vcf-block", type=int, default=1 << 14, help="records per block of --load-vcf (the command line's: max(--block_size, 2^14))")
+    ap.add_argument("--ingest-records", type=int, default=1 << 16, help="records of --load-vcf held in memory for the timing of sh_enet_ingest_calls alone")
     ap.add_argument("--python-reader", action="store_true")
     ap.add_argument("--tmp", default=None, help="directory for the packed cache of --ingest")
     ap.add_argument("--variants", type=int, default=100000)
@@ -182,6 +279,10 @@ def main():
         return ingest_stage(o)
     if o.load_kmers:
         return load_kmers_stage(o)
+    if o.write_vcf:
+        return write_vcf(o)
+    if o.load_vcf:
+        return load_vcf_stage(o)
     from pyseer_amd.engine import Engine
     from pyseer_amd.enet import EnetMatrix, assign_folds
     P, N = o.variants, o.samples
