@@ -363,6 +363,37 @@ int         sh_burden_fold(sh_ctx *ctx, const uint8_t *present, const uint8_t *m
                            const int32_t *csr_idx, int64_t n_variants, uint8_t *out_present, uint8_t *out_missing, int32_t *n_present, int32_t *n_missing);
 
 /* ---------------------------------------------------------------------------------------------
+ * Native Rtab reader (csrc/rtab_reader.cpp + csrc/rtab_kernels.hip; replaces the 'Rtab' branch of pyseer/input.py:301 read_variant for the
+ * GPU feed).  A presence/absence table -- plain text, as roary, panaroo, piggy or `unitig-caller --rtab` write it -- is framed on the host
+ * exactly as Python's text mode frames it (\n, \r\n, a lone \r; a last line without terminator), every line stripped at its end of what
+ * str.rstrip() strips among ASCII bytes, and split at its first tab into the name and the call text; the call text goes to the device as it
+ * stands and k_rtab_pack reduces every call to present (`1`) / missing (`.` or empty) / absent (`0`).  Bound to a context because it uses
+ * its device and stream; ctx == NULL selects the host restatement of the kernel (measurements, and checks where there is no device).
+ *   sh_rtab_open: `columns` are the sample columns of the header as the caller split them (the reference: header.rstrip().split()[1:]); the
+ *   reader skips the file's first line and does not parse it.  A column that names no sample is ignored; a sample without a column is absent
+ *   in every row.  A sample named by two columns is refused -- the reference lets the last call that is not `0` win, which OR-ing bits cannot
+ *   give -- with a message that begins "Rtab: duplicate sample column": the caller then reads the table line by line.
+ *   sh_rtab_next: up to max_rows lines -> per line a status and two packed rows over sample_names in the engine's layout (LSB first,
+ *   row_bytes as sh_lmm_batch): `present` and `missing` (a sample is never in both) with their popcounts.  status: 0 ok; 1 the line has no
+ *   calls ("No sample data found; is this a Rtab file?"); 2 the number of calls is not the header's ("Unexpected mismatch between header
+ *   and data row"); 3 a call that is none of `0`, `1`, `.`, empty, in any column ("Rtab file not binary") -- in this order of precedence,
+ *   the reference's.  A malformed line is a status and not an error, because a caller that selects lines by name passes over the others
+ *   unchecked; its rows are zeros.  Returns the number of lines, 0 at the end of the file, -1 on an I/O or HIP error (sh_last_error).
+ *   sh_rtab_names: the names of the LAST sh_rtab_next (everything before a line's first tab) as one blob + offsets (layout of
+ *   sh_reader_next), owned by the reader and valid until its next call; returns the blob's length.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sh_rtab sh_rtab;
+sh_rtab    *sh_rtab_open(sh_ctx *ctx, const char *path, const char *const *sample_names, int n_samples, const char *const *columns, int n_columns);
+void        sh_rtab_close(sh_rtab *r);
+int64_t     sh_rtab_next(sh_rtab *r, int64_t max_rows, int32_t *status, uint8_t *present, uint8_t *missing, int64_t row_bytes, int32_t *n_present,
+                         int32_t *n_missing);
+int64_t     sh_rtab_names(sh_rtab *r, const char **blob, const int64_t **name_off);
+/* bytes of call text handed to the tokeniser, lines delivered, kernel launches so far */
+int         sh_rtab_stats(sh_rtab *r, int64_t *call_bytes, int64_t *rows, int64_t *launches);
+/* how k_rtab_pack divides a line's call text: bytes per lane, per wavefront and per step of all lanes (tests place line ends there) */
+int         sh_rtab_partition(sh_rtab *r, int *lane_bytes, int *wave_bytes, int *step_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Whole-genome elastic net (csrc/enet_kernels.hip + csrc/enet_api.inc; replaces pyseer/enet.py load_all_vars :33-118, correlation_filter
  * :379-421 and the cvglmnet call of fit_enet :177-185).  One bit matrix of every variant that passed the filters stays on the device; the full
  * fit and each cross-validation fold are that matrix with other sample weights (a held-out sample has weight 0).

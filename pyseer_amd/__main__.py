@@ -10,7 +10,8 @@ tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 --lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 16).
 
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
-reader (--python-reader).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
+reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or
+line by line (--python-reader; also with --gpus, and for a header that names a sample twice).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
 and --pres and --python-reader line by line.  Not supported (out of scope): --wg rf / blup, BCF, and --gpus / the packed cache with a VCF.
 """
 import argparse
@@ -88,7 +89,7 @@ from . import __version__
 from .classes import Seer, LMM, FLAG_FILTER, FLAG_PREFILTER, notes_from_flags
 from .input import (check_kmers_gzipped, check_packed_cache, plan_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
                     iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_native_multi, iter_packed_blocks_cached,
-                    iter_packed_blocks_vcf_native, load_burden,
+                    iter_packed_blocks_vcf_native, iter_packed_blocks_rtab_native, load_burden,
                     PackedCacheWriter, packed_cache_complete)
 from .lmm import initialise_lmm, mask_like_fit_lmm
 from .model import fit_null, covariate_block
@@ -173,7 +174,7 @@ def get_options(argv=None):
     ot.add_argument('--no-dedup', action='store_true', default=False,
                     help='Test every variant separately [Default: each distinct presence pattern of a block is tested once]')
     ot.add_argument('--python-reader', action='store_true', default=False,
-                    help='Parse k-mer and VCF files with the Python reader instead of the native one')
+                    help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
     ot.add_argument('--python-sink', action='store_true', default=False,
                     help='Format every output row in Python (one result tuple per variant) instead of the native block sink')
     ot.add_argument('--serial-sink', action='store_true', default=False,
@@ -431,6 +432,9 @@ def main(argv=None):
     var_type, var_file = ("kmers", kmer_files[0]) if kmer_files else (("vcf", options.vcf) if options.vcf else ("Rtab", options.pres))
     native = (var_type == "kmers") and not options.python_reader
     native_vcf = (var_type == "vcf") and not options.python_reader
+    # (the Rtab reader is bound to one context: --gpus keeps the line-by-line reader, and so does a run that names a packed cache)
+    native_rtab = ((var_type == "Rtab") and not options.python_reader and options.gpus is None
+                   and not (options.load_packed or options.save_packed or options.packed_cache or options.packed_part))
     burden_regions = None
     if options.burden:
         import collections as _collections
@@ -445,7 +449,7 @@ def main(argv=None):
     if native_vcf:
         if options.burden:
             load_burden(options.burden, burden_regions)
-    elif not native:
+    elif not native and not native_rtab:
         infile, sample_order = open_variant_file(var_type, var_file, options.burden, burden_regions, options.uncompressed)
     patterns = open(options.output_patterns, 'wb') if options.output_patterns else None
 
@@ -501,6 +505,9 @@ def main(argv=None):
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
         blocks = iter_packed_blocks_vcf_native(p, var_file, engs[0], options.min_af, options.max_af, options.max_missing, options.block_size,
                                                burden_regions=(list(burden_regions) if options.burden else None))
+    elif native_rtab:
+        # (as above: the calls are tokenised on the first context's device; a header that names a sample twice takes the line reader by itself)
+        blocks = iter_packed_blocks_rtab_native(p, var_file, engs[0], options.min_af, options.max_af, options.max_missing, options.block_size)
     else:
         blocks = iter_packed_blocks(p, var_type, infile, all_strains, sample_order, options.min_af, options.max_af,
                                     options.max_missing, options.uncompressed, options.block_size,

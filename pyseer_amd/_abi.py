@@ -105,6 +105,13 @@ SIGNATURES = {
     "sh_vcf_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sh_burden_fold": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, c_u8p, c_u8p,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # the native Rtab reader (csrc/rtab_reader.cpp, csrc/rtab_kernels.hip)
+    "sh_rtab_open": (C.c_void_p, [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int]),
+    "sh_rtab_close": (None, [C.c_void_p]),
+    "sh_rtab_next": (C.c_int64, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), c_u8p, c_u8p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sh_rtab_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "sh_rtab_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sh_rtab_partition": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # the whole-genome elastic net (csrc/enet_kernels.hip, csrc/enet_api.inc); the structs are EnetOpts / EnetOut below
     "sh_enet_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "sh_enet_append": (C.c_int, [C.c_void_p, c_u8p, c_u8p, c_u8p, C.c_int64]),

@@ -22,6 +22,8 @@
 #include "lmm_params.h"
 #include "vcf_kernels.h"
 #include "vcf_reader.h"
+#include "rtab_kernels.h"
+#include "rtab_reader.h"
 #include "enet_params.h"
 extern "C" {
 hipError_t shk_sim_accumulate(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, double min_af, double max_af,
@@ -1159,6 +1161,7 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "job_api.inc"
 #include "job_run.inc"
 #include "vcf_api.inc"
+#include "rtab_api.inc"
 #include "enet_api.inc"
 
 }  // extern "C"

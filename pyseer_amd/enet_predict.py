@@ -6,7 +6,8 @@ MODEL is what `python -m pyseer_amd --wg enet --save-enet-model` wrote (text), o
 sample is the intercept, plus its covariates times their slopes, plus the slope of every model variant it carries, added in the order of the
 input (k_enet_predict keeps that order: the printed numbers are the reference's, digit for digit).  K-mers and the packed cache come as raw
 blocks from the native reader and are matched to the model by name in the library (sh_nameset_*); a VCF comes through the native VCF
-reader; --pres, --burden and --python-reader go line by line through read_variant.  All routes print the same bytes.
+reader and an Rtab (--pres) through the native Rtab reader; --burden and --python-reader go line by line through read_variant.  All routes
+print the same bytes.
 """
 import argparse
 import collections
@@ -37,7 +38,7 @@ def get_options(argv=None):
     covariates.add_argument('--use-covariates', default=None, nargs='*', help='Covariates to use. Format is "2 3q 4" (q for quantitative)')
     ot = parser.add_argument_group('Other')
     ot.add_argument('--gpu', type=int, default=0, help='GPU index [Default: 0]')
-    ot.add_argument('--python-reader', action='store_true', default=False, help='Parse k-mer and VCF files with the Python reader instead of the native one')
+    ot.add_argument('--python-reader', action='store_true', default=False, help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
     ot.add_argument('--load-packed', default=None, help='Read k-mers from a packed cache written by an earlier run over the same samples instead of --kmers')
     ot.add_argument('--block_size', type=int, default=3000, help='Number of variants parsed at a time')
     options = parser.parse_args(argv)
@@ -132,8 +133,44 @@ def _predict_vcf_native(options, samples, engine, model, predictor):
         names.close()
 
 
+def _predict_rtab_native(options, samples, engine, model, predictor):
+    """Lines of the native Rtab reader, matched by name.  Only a matched line is looked at: one that is malformed raises read_variant's
+    ValueError, after the matched lines before it have said what read_variant says of them; a malformed line the model does not name is passed
+    over, as read_variant returns before its checks for a name outside the keep_list.  Returns False, with nothing read, for a header that
+    names a sample twice (the caller reads line by line)."""
+    from .enet import NameSet
+    from .input import NativeRtabReader, RtabDuplicateSample, RTAB_ERRORS
+    try:
+        reader = NativeRtabReader(options.pres, samples, engine, max(options.block_size, 1))
+    except RtabDuplicateSample:
+        return False
+    names = NameSet(model.names)
+    try:
+        for blk in reader.raw_blocks():
+            blob, off = blk["blob"], blk["off"]
+            rows, which = names.match(blob, off)
+            bad = np.nonzero(blk["status"][rows])[0]
+            upto = int(bad[0]) if bad.size else rows.size                 # matched lines before the first malformed one
+            for r in rows[:upto][(blk["n_present"][rows[:upto]] + blk["n_missing"][rows[:upto]]) == 0]:
+                sys.stderr.write("No observations of " + blob[off[r]:off[r + 1]].decode() + " in selected samples\n")
+            if bad.size:
+                raise ValueError(RTAB_ERRORS[int(blk["status"][rows[upto]])])
+            model.met[which] = True
+            use = model.beta[which] != 0
+            sel = rows[use]
+            if sel.size:
+                miss = blk["missing"] if np.any(blk["n_missing"][sel] > 0) else None
+                predictor.add(blk["present"], sel, model.beta[which[use]], model.flip[which[use]], missing=miss)
+            if names.left == 0:
+                break
+    finally:
+        reader.close()
+        names.close()
+    return True
+
+
 def _predict_lines(options, p, model, predictor, var_type, var_file):
-    """--pres, --burden and --python-reader: the reference's loop over read_variant (enet_predict.py:159-179), its rows packed in blocks."""
+    """--burden and --python-reader (and an Rtab whose header names a sample twice): the reference's loop over read_variant (enet_predict.py:159-179), its rows packed in blocks."""
     from .input import open_variant_file, read_variant
     from .packing import row_bytes_for
     n, rb = len(p), row_bytes_for(len(p))
@@ -245,6 +282,8 @@ def main(argv=None):
             _predict_kmer_blocks(blocks, model, predictor)
         elif var_type == "vcf" and not options.python_reader and not options.burden:
             _predict_vcf_native(options, samples, engine, model, predictor)
+        elif var_type == "Rtab" and not options.python_reader and _predict_rtab_native(options, samples, engine, model, predictor):
+            pass
         else:
             _predict_lines(options, p, model, predictor, var_type, var_file)
         link = predictor.finish()

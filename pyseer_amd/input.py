@@ -853,6 +853,150 @@ def iter_call_blocks_vcf_native(p, path, engine, block_size, burden_regions=None
         reader.close()
 
 
+RTAB_ERRORS = {1: 'No sample data found; is this a Rtab file?',            # row status of sh_rtab_next -> read_variant's ValueError (input.py:377-383)
+               2: 'Unexpected mismatch between header and data row',
+               3: 'Rtab file not binary'}
+LAST_RTAB_LAUNCHES = None     # kernel launches (sh_rtab_stats) of the last native Rtab reader this process closed; None: none was opened
+
+
+class RtabDuplicateSample(ValueError):
+    """The header names a phenotype sample in more than one column: sh_rtab_open refuses, the callers read the table line by line."""
+
+
+class NativeRtabReader(object):
+    """Blocks of Rtab lines through libseerhip's reader (sh_rtab_*: csrc/rtab_reader.cpp on the host, k_rtab_pack on the device): per line the
+    name, a status (0 ok, else a key of RTAB_ERRORS; such a line has rows of zeros) and the packed present / missing rows over `sample_names`.
+    The header is split here, with the reference's own expression, and handed to the library, which skips the first line.
+    engine: the Engine whose device and stream the reader uses; None selects the library's host restatement of the kernel.
+    Raises RtabDuplicateSample when two columns name the same phenotype sample: the reference lets the last call that is not `0` win there,
+    which no OR of bits reproduces, so every caller in this package then takes the Python reader (read_variant) and prints the same bytes."""
+
+    def __init__(self, path, sample_names, engine=None, block_size=3000):
+        import ctypes as C
+        from . import _abi
+        self._C, self._abi = C, _abi
+        self._lib = _abi.load()
+        self.samples = [str(x) for x in sample_names]
+        self.n = len(self.samples)
+        self._engine = engine                               # (kept alive: the reader holds its context)
+        with open(path) as fh:
+            header = fh.readline().rstrip()
+        self.columns = [str(x) for x in header.split()[1:]]
+        arr = (C.c_char_p * self.n)(*[x.encode() for x in self.samples])
+        cols = (C.c_char_p * max(1, len(self.columns)))(*[x.encode() for x in self.columns])
+        h = self._lib.sh_rtab_open(engine._h if engine is not None else None, str(path).encode(), arr, self.n, cols, len(self.columns))
+        if not h:
+            msg = self._lib.sh_last_error().decode()
+            if msg.startswith("Rtab: duplicate sample column"):
+                raise RtabDuplicateSample(msg)
+            raise IOError(msg)
+        self._h = C.c_void_p(h)
+        self.block_size = int(block_size)
+        self.row_bytes = row_bytes_for(self.n)
+
+    def close(self):
+        global LAST_RTAB_LAUNCHES
+        if getattr(self, "_h", None):
+            LAST_RTAB_LAUNCHES = self.stats()["launches"]
+            self._lib.sh_rtab_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        C = self._C
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._abi.check(self._lib.sh_rtab_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"call_bytes": a.value, "rows": b.value, "launches": c.value}
+
+    def partition(self):
+        """Bytes of call text per lane, per wavefront and per step of k_rtab_pack as this reader launches it."""
+        C = self._C
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._abi.check(self._lib.sh_rtab_partition(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"lane": a.value, "wave": b.value, "step": c.value}
+
+    def raw_blocks(self):
+        """dict per block: blob / off (names), status, skip (zeros), present, missing (packed rows), n_present, n_missing."""
+        C = self._C
+        i32 = C.POINTER(C.c_int32)
+        bs = self.block_size
+        while True:
+            status = np.zeros(bs, dtype=np.int32); n_p = np.zeros(bs, dtype=np.int32); n_m = np.zeros(bs, dtype=np.int32)
+            present = np.zeros((bs, self.row_bytes), dtype=np.uint8); missing = np.zeros((bs, self.row_bytes), dtype=np.uint8)
+            nv = self._lib.sh_rtab_next(self._h, bs, status.ctypes.data_as(i32), present.ctypes.data_as(self._abi.c_u8p),
+                                        missing.ctypes.data_as(self._abi.c_u8p), self.row_bytes, n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32))
+            if nv < 0:
+                raise IOError(self._lib.sh_last_error().decode())
+            if nv == 0:
+                return
+            blob_p, off_p = C.c_void_p(0), C.c_void_p(0)
+            nb = self._lib.sh_rtab_names(self._h, C.byref(blob_p), C.byref(off_p))
+            blob = C.string_at(blob_p.value, nb) if nb > 0 else b""
+            off = np.frombuffer(C.string_at(off_p.value, 8 * (nv + 1)), dtype=np.int64).copy()
+            yield {"blob": blob, "off": off, "status": status[:nv], "skip": np.zeros(nv, dtype=np.int32), "present": present[:nv],
+                   "missing": missing[:nv], "n_present": n_p[:nv], "n_missing": n_m[:nv]}
+
+
+def _rtab_call_blocks(reader):
+    """(CallBlock, error) per block of the reader: error is None, or the ValueError of the block's first malformed line -- the block then
+    holds only the lines before it, and is the last."""
+    for rb in reader.raw_blocks():
+        bad = np.nonzero(rb["status"])[0]
+        nv = int(bad[0]) if bad.size else rb["status"].shape[0]
+        cb = CallBlock(rb["blob"][:rb["off"][nv]], rb["off"][:nv + 1], rb["skip"][:nv], rb["present"][:nv], rb["missing"][:nv], rb["n_present"][:nv],
+                       rb["n_missing"][:nv], [""] * nv)
+        yield cb, (ValueError(RTAB_ERRORS[int(rb["status"][nv])]) if bad.size else None)
+        if bad.size:
+            return
+
+
+def iter_packed_blocks_rtab_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True):
+    """The PackedBlock stream of iter_packed_blocks(p, 'Rtab', ...) fed by the native reader: same names, af (present + missing over n), sample
+    lists, statuses, dense k for rows with missing calls, patterns and stderr lines.  A malformed line raises read_variant's ValueError once
+    every complete block before it has been yielded and the lines before it in its own block have said what read_variant says of them -- the
+    point at which the line-by-line route raises.  A header that names a phenotype sample twice: the line-by-line route itself."""
+    samples = [str(x) for x in p.index]
+    order = sorted(range(len(samples)), key=lambda i: samples[i])
+    n = len(samples)
+    try:
+        reader = NativeRtabReader(path, samples, engine, block_size)
+    except RtabDuplicateSample:
+        infile, sample_order = open_variant_file("Rtab", path)
+        for blk in iter_packed_blocks(p, "Rtab", infile, set(p.index), sample_order, min_af, max_af, max_missing, False, block_size, want_patterns=want_patterns):
+            yield blk
+        return
+    try:
+        for cb, error in _rtab_call_blocks(reader):
+            blk = _vcf_packed_block(n, samples, order, cb.names, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing,
+                                    min_af, max_af, max_missing, want_patterns)
+            if error is not None:
+                raise error
+            yield blk
+    finally:
+        reader.close()
+
+
+def iter_call_blocks_rtab_native(p, path, engine, block_size):
+    """The CallBlock stream of an Rtab for the whole-genome models (enet.load_all_vars_calls): every line in input order, before any AF window.
+    A malformed line raises read_variant's ValueError after the lines before it have been yielded (a last, shorter block), so that the
+    consumer has said of them what the line-by-line route says before it raises.  Not for a header that names a phenotype sample twice
+    (RtabDuplicateSample: the caller keeps load_all_vars)."""
+    reader = NativeRtabReader(path, [str(x) for x in p.index], engine, block_size)
+    try:
+        for cb, error in _rtab_call_blocks(reader):
+            if len(cb):
+                yield cb
+            if error is not None:
+                raise error
+    finally:
+        reader.close()
+
+
 def prefetched(iterable, depth=2):
     """Run `iterable` in a background thread, `depth` items ahead.  The native reader spends its time inside ctypes calls (GIL
     released: inflate + OpenMP parse), so block k+1 is read and packed while block k is on the GPU / being formatted."""

@@ -29,7 +29,7 @@ def get_options(argv=None):
                         help='Uncompressed kmers file [Default: gzipped]')
     parser.add_argument('--gpu', type=int, default=0, help='Device index [Default: 0]')
     parser.add_argument('--python-reader', action='store_true', default=False,
-                        help='Parse k-mer and VCF files with the Python reader instead of the native one')
+                        help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
     parser.add_argument('--version', action='version', version='%(prog)s ' + __version__)
     return parser.parse_args(argv)
 
@@ -81,12 +81,14 @@ class SimilarityAccumulator(object):
 def similarity_matrix(p, var_type, infile, path, all_strains, sample_order, min_af, max_af, max_missing, uncompressed,
                       device=0, python_reader=False, progress=None):
     """The loop of similarity.py:99-113 over PackedBlocks."""
-    from .input import iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_vcf_native
+    from .input import iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_rtab_native, iter_packed_blocks_vcf_native
     acc = SimilarityAccumulator(len(p), device=device)
     if var_type == "kmers" and not python_reader:
         blocks = iter_packed_blocks_native(p, path, min_af, max_af, block_size)
     elif var_type == "vcf" and not python_reader:       # the sample columns are tokenised on the accumulator's device (pyseer/similarity.py:86-88)
         blocks = iter_packed_blocks_vcf_native(p, path, acc.engine, min_af, max_af, max_missing, block_size, want_patterns=False)
+    elif var_type == "Rtab" and not python_reader:      # the calls likewise (k_rtab_pack)
+        blocks = iter_packed_blocks_rtab_native(p, path, acc.engine, min_af, max_af, max_missing, block_size, want_patterns=False)
     else:
         blocks = iter_packed_blocks(p, var_type, infile, all_strains, sample_order, min_af, max_af, max_missing,
                                     uncompressed, block_size, want_patterns=False)
@@ -130,8 +132,9 @@ def main(argv=None):
         if options.python_reader:
             infile, sample_order = open_variant_file("vcf", options.vcf)
     else:
-        var_type = "Rtab"
-        infile, sample_order = open_variant_file("Rtab", options.pres)
+        var_type, path = "Rtab", options.pres
+        if options.python_reader:
+            infile, sample_order = open_variant_file("Rtab", options.pres)
     sys.stderr.write("Reading in variants\n")
     K = similarity_matrix(p, var_type, infile, path, all_strains, sample_order, options.min_af, options.max_af,
                           options.max_missing, options.uncompressed, device=options.gpu,
