@@ -297,6 +297,7 @@ int     sh_job_depth(sh_job *job);     /* blocks that may be submitted and not y
 int     sh_job_set_lineage(sh_job *job, const char *const *labels, int n_labels, int per_variant);
 int     sh_job_set_patterns(sh_job *job, int on);
 int     sh_job_patterns(sh_job *job, const char **text, int64_t *nbytes);
+int     sh_job_set_pattern_count(sh_job *job, int on);   /* the job's context must have a set begun: the pattern set below */
 int     sh_job_set_samples(sh_job *job, const char *names, const int64_t *name_off, const int32_t *order, int n);
 /* The whole block loop of one stream of a packed cache (pyseer_amd/input.py PackedCacheWriter: the `--save-packed` / `--load-packed` file) in
  * one call -- the loop over load_var_block / fit / print of pyseer/__main__.py:541-593, 777-827 for part `part_i` of `part_n` contiguous ranges
@@ -332,6 +333,31 @@ int     sh_host_pool_workers(void);
 int     sh_host_cpu_seconds(char *buf, int cap);
 /* the largest number of threads that were inside sh_format_rows / sh_format_records at the same time (reset != 0 clears it): tests */
 int     sh_format_concurrency_max(int reset);
+
+/* ---------------------------------------------------------------------------------------------
+ * The run-wide set of distinct presence patterns (--count-patterns).  Replaces scripts/count_patterns.py of the reference, which takes
+ * the file --output-patterns wrote (one base64 md5 line per tested variant, pyseer/input.py:710-723), runs `LC_ALL=C sort -u | wc -l`
+ * over it and prints the Bonferroni threshold alpha / count.  Two variants have the same md5 exactly when their presence rows are equal, so
+ * the count is the number of distinct packed rows: the set keeps one 128-bit key per row (two independently seeded 64-bit sums over the
+ * row's 64-bit words and their indices, the N sample bits only; n distinct rows collide with probability about n^2 / 2^129, the order of
+ * md5's own) in an open-addressing table in device memory that lives across the blocks of a run and doubles before its load passes 1/2.
+ * No md5, no text, no sort.
+ *   begin: initial_slots 0 = 2^20, else a power of two >= 1024.  One set per context, until end (or sh_destroy).
+ *   add_rows: V host rows as sh_lmm_batch takes them, every row inserted; add_rows_dev: the same rows in device memory.
+ *   add_keys: n ready-made keys of two 64-bit words each, e.g. the 16 bytes of an md5 digest made on the host (rows with missing calls
+ *     never reach the device).  A half equal to ~0 is stored as 0: (~0, b) and (0, b) count as one key, and so do (a, ~0) and (a, 0).
+ *   count: waits for the inserts queued so far (the lanes' included); distinct keys, the table's slots, how often it grew.
+ *   hash_rows: the keys the device gives the same rows (2 V words), on the host, no context: add_keys of them equals add_rows.
+ * A job with sh_job_set_pattern_count on inserts the rows sh_job_set_patterns would digest -- every TESTED row of a block -- on the stream of
+ * the block's own kernels, with or without sh_job_set_patterns.  Inserts and counts are asynchronous to the caller except where stated.
+ * ------------------------------------------------------------------------------------------- */
+int     sh_patset_begin(sh_ctx *ctx, int64_t initial_slots);
+int     sh_patset_add_rows(sh_ctx *ctx, const uint8_t *bits, int64_t row_bytes, int64_t V);
+int     sh_patset_add_rows_dev(sh_ctx *ctx, const void *d_bits, int64_t row_bytes, int64_t V);
+int     sh_patset_add_keys(sh_ctx *ctx, const uint64_t *keys, int64_t n);
+int     sh_patset_count(sh_ctx *ctx, int64_t *distinct, int64_t *slots, int64_t *growths);
+int     sh_patset_end(sh_ctx *ctx);
+int     sh_patset_hash_rows(const uint8_t *bits, int64_t row_bytes, int64_t V, int n_samples, uint64_t *keys);
 
 /* ---------------------------------------------------------------------------------------------
  * Native VCF reader (csrc/vcf_reader.cpp + csrc/vcf_kernels.hip; replaces the 'vcf' branch of pyseer/input.py:301 read_variant and

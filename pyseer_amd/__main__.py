@@ -155,6 +155,10 @@ def get_options(argv=None):
     ot.add_argument('--print-samples', action='store_true', default=False, help='Print sample lists [Default: hide]')
     ot.add_argument('--print-filtered', action='store_true', default=False, help='Print filtered variants [Default: hide]')
     ot.add_argument('--output-patterns', default=False, help='File to print patterns to, useful for finding pvalue threshold')
+    ot.add_argument('--count-patterns', default=None, metavar='FILE',
+                    help='Count the distinct presence patterns of the tested variants on the GPU while the run goes and write the count and the '
+                         'Bonferroni threshold to FILE, as scripts/count_patterns.py prints them for an --output-patterns file')
+    ot.add_argument('--pattern-alpha', type=float, default=0.05, help='Family-wise error rate of the --count-patterns threshold [Default: 0.05]')
     ot.add_argument('--uncompressed', action='store_true', default=False, help='Uncompressed kmers file [Default: gzipped]')
     ot.add_argument('--cpu', type=int, default=1, help='Accepted for compatibility; the tests run on the GPU')
     ot.add_argument('--block_size', type=int, default=3000, help='Number of variants parsed and sent to the GPU at a time')
@@ -208,6 +212,14 @@ def main(argv=None):
             options.cpu_eigh = True
     if options.burden and not options.vcf:
         _die('Burden test can only be performed with VCF input\n')
+    if options.count_patterns:
+        # (the set of distinct patterns lives on one device, in one process: a union across devices or processes is not built)
+        if options.wg:
+            _die("Whole genome model does not produce patterns. Re-run without --count-patterns.\n")
+        if options.gpus is not None and (len(options.gpus.split(",")) > 1 if "," in options.gpus else int(options.gpus) > 1):
+            _die("--count-patterns counts on one device: it is not available with more than one device in --gpus\n")
+        if options.packed_part:
+            _die("--count-patterns counts one whole run: it is not available with --packed-part\n")
     if options.vcf and (options.gpus is not None or options.save_packed or options.load_packed or options.packed_cache or options.packed_part):
         _die('--gpus and the packed cache (--save-packed / --load-packed / --packed-cache / --packed-part) are not available with --vcf\n')
     if options.lmm and options.wg:
@@ -488,18 +500,26 @@ def main(argv=None):
     job_block = options.block_size if (options.print_filtered or lmm_block_lineage or not job_path) else max(options.block_size, 1 << 18)
     # the reader runs as far ahead as the job stream holds blocks in flight (fixed effects: 2 + lanes, include/seerhip.h sh_job_depth)
     job_ahead = (2 + engs[0].get_lanes()) if (job_path and not options.lmm and engs) else 2
+    # --count-patterns: the set of distinct patterns on the first (the only) device.  The job stream inserts every tested row there itself
+    # (sh_job_set_pattern_count: no md5); the other routes make hash_pattern on the host, and the 16 digest bytes are the keys -- so are those
+    # of rows with missing calls, which never reach the device (a row with a NaN never equals one without: the count stays exact)
+    count_set = None
+    if options.count_patterns:
+        from .engine import PatternSet
+        count_set = PatternSet(engs[0])
+    want_pat = bool(options.output_patterns) or (count_set is not None and not job_path)
     if options.load_packed:
         blocks = iter_packed_blocks_cached(p, options.load_packed, options.min_af, options.max_af, job_block,
-                                           want_patterns=bool(options.output_patterns), want_samples=options.print_samples,
+                                           want_patterns=want_pat, want_samples=options.print_samples,
                                            raw=job_path, device=(engs[0].device if (job_path and engs) else None), ahead=job_ahead)
     elif native and len(kmer_files) > 1:
         blocks = iter_packed_blocks_native_multi(p, kmer_files, options.min_af, options.max_af, job_block,
-                                                 want_patterns=bool(options.output_patterns), want_samples=options.print_samples, raw=job_path)
+                                                 want_patterns=want_pat, want_samples=options.print_samples, raw=job_path)
     elif native:
         if options.save_packed:
             cache_out = PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
         blocks = iter_packed_blocks_native(p, var_file, options.min_af, options.max_af, job_block,
-                                           want_patterns=bool(options.output_patterns), want_samples=options.print_samples,
+                                           want_patterns=want_pat, want_samples=options.print_samples,
                                            save_to=cache_out, raw=job_path)
     elif native_vcf:
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
@@ -539,7 +559,7 @@ def main(argv=None):
         from .engine import Job
         jobs = [Job(e_, options.lmm, options.print_filtered, lineage_labels=(lineage_dict if options.lineage else None),
                     lineage_per_variant=options.lmm_lineage_per_variant, patterns=write_patterns is not None,
-                    sample_names=([str(x) for x in p.index] if options.print_samples else None)) for e_ in engs]
+                    sample_names=([str(x) for x in p.index] if options.print_samples else None), pattern_count=count_set is not None) for e_ in engs]
         prefilter = tested = printed = 0
         order = collections.deque()                           # the job each block in flight went to, in input order
 
@@ -596,7 +616,7 @@ def main(argv=None):
             pat_file.flush()
         job = Job(eng_, options.lmm, options.print_filtered, lineage_labels=(lineage_dict if options.lineage else None),
                   lineage_per_variant=options.lmm_lineage_per_variant, patterns=pat_file is not None,
-                  sample_names=([str(x) for x in p.index] if options.print_samples else None))
+                  sample_names=([str(x) for x in p.index] if options.print_samples else None), pattern_count=count_set is not None)
         try:
             pf_, te_, pr_, nb_ = job.run_packed(options.load_packed, part, job_block, use_dma=_route.route("dma", "1") != "0", out_fd=out_file.fileno(),
                                                 pat_fd=(pat_file.fileno() if pat_file is not None else -1), stop=stop_c)
@@ -1077,7 +1097,27 @@ def main(argv=None):
         prefilter, tested, printed = run_stream_job(engs, blocks, write_stdout, tms[0], None, None if patterns is None else patterns.write)
         thread_cpu["stream 0 loop thread"] = _time.thread_time() - t_th
     else:
-        prefilter, tested, printed = run_stream(engs, blocks, write_stdout, None if patterns is None else patterns.write, tms[0])
+        wp = None if patterns is None else patterns.write
+        flush_keys = None
+        if count_set is not None:
+            from .count_patterns import digests_of_lines
+            to_file, held = wp, []
+
+            def flush_keys():
+                if held:
+                    count_set.add_keys(digests_of_lines(b''.join(held)))
+                    del held[:]
+
+            def wp(b):                                    # (the tuple path writes one line per variant: the keys go to the device in batches)
+                if to_file is not None:
+                    to_file(b)
+                if len(b):
+                    held.append(bytes(b))
+                    if len(held) >= 4096 or len(b) >= 25 * 4096:
+                        flush_keys()
+        prefilter, tested, printed = run_stream(engs, blocks, write_stdout, wp, tms[0])
+        if flush_keys is not None:
+            flush_keys()
 
     if cli_timing:
         # the host budget of the block loop (tools/gpu_e2e_job.py -> profiles/r05/host_budget.json): process CPU seconds (user + sys, every
@@ -1117,6 +1157,12 @@ def main(argv=None):
                          % (since_start, t_setup - t_inputs, tms[0]["t0w"] - t_setup, since_start + _time.time() - t_inputs))
     if patterns is not None:
         patterns.close()
+    if count_set is not None:
+        from .count_patterns import result_text
+        n_patterns = count_set.count()
+        count_set.close()
+        with open(options.count_patterns, 'w') as fh:
+            fh.write(result_text(n_patterns, options.pattern_alpha))
     if cache_out is not None:
         cache_out.close()
     for e_ in engs:

@@ -84,6 +84,7 @@ SIGNATURES = {
     "sh_job_set_lineage": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int]),
     "sh_job_set_patterns": (C.c_int, [C.c_void_p, C.c_int]),
     "sh_job_patterns": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "sh_job_set_pattern_count": (C.c_int, [C.c_void_p, C.c_int]),
     "sh_job_set_samples": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int]),
     "sh_job_run_packed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "sh_host_register": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
@@ -94,6 +95,14 @@ SIGNATURES = {
     "sh_host_pool_workers": (C.c_int, []),
     "sh_host_cpu_seconds": (C.c_int, [C.c_char_p, C.c_int]),
     "sh_format_concurrency_max": (C.c_int, [C.c_int]),
+    # the run-wide set of distinct presence patterns (csrc/patset_kernels.hip, csrc/patset_api.inc)
+    "sh_patset_begin": (C.c_int, [C.c_void_p, C.c_int64]),
+    "sh_patset_add_rows": (C.c_int, [C.c_void_p, c_u8p, C.c_int64, C.c_int64]),
+    "sh_patset_add_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "sh_patset_add_keys": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]),
+    "sh_patset_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sh_patset_end": (C.c_int, [C.c_void_p]),
+    "sh_patset_hash_rows": (C.c_int, [c_u8p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_uint64)]),
     # the native VCF reader (csrc/vcf_reader.cpp, csrc/vcf_kernels.hip)
     "sh_vcf_open": (C.c_void_p, [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
     "sh_vcf_close": (None, [C.c_void_p]),

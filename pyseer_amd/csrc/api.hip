@@ -25,6 +25,7 @@
 #include "rtab_kernels.h"
 #include "rtab_reader.h"
 #include "enet_params.h"
+#include "patset_hash.h"
 extern "C" {
 hipError_t shk_sim_accumulate(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, double min_af, double max_af,
                               int af_on, uint64_t *keep, uint64_t *S, int NS, unsigned long long *Kacc);
@@ -58,6 +59,10 @@ int64_t format_records_samples(const char *, const int64_t *, const int32_t *, i
                                const uint8_t *, const int32_t *, const char *const *, int, const uint32_t *, const char **, const uint8_t *, int64_t, const char *,
                                const int64_t *, const int32_t *);
 hipError_t shk_job_patterns(hipStream_t, const uint64_t *, int64_t, int64_t, int, const uint32_t *, int *, long long *, uint32_t *, char *, char *);
+// patset_kernels.hip
+hipError_t shk_ps_insert_rows(hipStream_t, const uint8_t *, int64_t, int64_t, int, const uint32_t *, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
+hipError_t shk_ps_insert_keys(hipStream_t, const uint64_t *, int64_t, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
+hipError_t shk_ps_rehash(hipStream_t, const unsigned long long *, const unsigned long long *, int64_t, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
 #define JOB_ROWS_PER_BLOCK_HOST 1024
 // enet_kernels.hip
 hipError_t shk_enet_store(hipStream_t, const uint8_t *, const uint8_t *, const uint8_t *, int64_t, int, int, uint64_t *);
@@ -110,6 +115,7 @@ template <typename T> static hipError_t dmalloc(T **p, size_t n)
 struct sh_lanes;
 struct EnetState;                        // enet_api.inc
 struct PredictState;                     // enet_api.inc
+struct PatSet;                           // patset_api.inc
 // what sh_glm_setup was called with: the lanes of the context (lanes_api.inc) are set up from it
 struct GlmSetupArgs { std::vector<double> y, W; int q = 0, continuous = 0, force_firth = 0; double null_llf = 0, null_firth = 0, pret = 1, lrtt = 1;
                       std::string route; };   // (route: the SEERHIP_ROUTE string the set-up ran under)
@@ -188,6 +194,8 @@ struct sh_ctx {
     EnetState *enet = nullptr;
     // ---- the accumulator of a saved model's predictions (sh_predict_*)
     PredictState *predict = nullptr;
+    // ---- the run-wide set of distinct presence patterns (sh_patset_*)
+    PatSet *patset = nullptr;
 };
 
 // ---- small device -> host read-backs (list lengths, counts) WITHOUT the copy engine ------------------------------------------------------------
@@ -211,6 +219,7 @@ static int readback_sync(sh_ctx *c, hipStream_t st, const int *a, const int *b, 
 static void lanes_destroy(sh_ctx *c);
 static void enet_free(sh_ctx *c);
 static void predict_free(sh_ctx *c);
+static void patset_free(sh_ctx *c);
 static int lanes_wait(sh_ctx *c);
 static void lanes_set_timing(sh_ctx *c, int on);
 static int lanes_add_timing(sh_ctx *c, double *total_ms, int64_t *launches);
@@ -576,6 +585,7 @@ void sh_destroy(sh_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     lanes_destroy(c);
+    patset_free(c);
     enet_free(c);
     predict_free(c);
     free_ws(c);
@@ -1158,6 +1168,7 @@ int sh_sim_finish(sh_ctx *c, double *K)
 
 #include "glm_api_impl.inc"
 #include "lanes_api.inc"
+#include "patset_api.inc"
 #include "job_api.inc"
 #include "job_run.inc"
 #include "vcf_api.inc"

@@ -47,6 +47,8 @@ struct sh_job {
     // last collected, until the next collect
     int patterns = 0;
     std::vector<char> pat_text; int64_t pat_n = 0;
+    // --count-patterns (sh_job_set_pattern_count): the same rows go into the context's set of distinct patterns (patset_api.inc), no md5
+    int pattern_count = 0;
     // --print-samples (sh_job_set_samples): the sample names in the order the reference lists them (sorted), for the printed rows' two lists
     std::string smp_blob; std::vector<int64_t> smp_off; std::vector<int32_t> smp_order;
 };
@@ -132,6 +134,10 @@ static int job_compute_on(sh_job *j, JobSlot &s, sh_ctx *k)
     if (rc) return rc;
     HIPCHK(shk_job_select(k->stream, s.d_flags, s.d_out, s.V, j->nrow, j->lmm, j->print_filtered, s.d_bcount, s.d_hdr, slot_hdr(s), slot_idx(s), slot_flags(s),
                           slot_cols(s), s.cap_res_rows, j->lin_mode == 1 ? s.d_sel : nullptr));
+    if (j->pattern_count) {
+        // the rows as submitted (the batch's own copy may be AF-compacted, de-duplicated or complemented), behind the flags they are chosen by
+        rc = patset_insert_rows(j->c, k->stream, s.d_bits, s.row_bytes, s.V, s.d_flags); if (rc) return rc;
+    }
     const int64_t Vpad = (s.V + 255) / 256 * 256;
     if (j->lin_mode == 1 || j->patterns) {
         // the block's rows repacked into this context's workspace, behind the batch that used it (whose own copy may be AF-compacted,
@@ -206,6 +212,15 @@ int sh_job_set_patterns(sh_job *j, int on)
     if (!j) return fail(SH_EINVAL, "null job");
     if (j->n_submitted != j->n_collected) return fail(SH_EINVAL, "sh_job_set_patterns: blocks are in flight");
     j->patterns = on ? 1 : 0;
+    return SH_OK;
+}
+
+int sh_job_set_pattern_count(sh_job *j, int on)
+{
+    if (!j) return fail(SH_EINVAL, "null job");
+    if (j->n_submitted != j->n_collected) return fail(SH_EINVAL, "sh_job_set_pattern_count: blocks are in flight");
+    if (on && !j->c->patset) return fail(SH_EINVAL, "sh_job_set_pattern_count: sh_patset_begin has not run on the job's context");
+    j->pattern_count = on ? 1 : 0;
     return SH_OK;
 }
 

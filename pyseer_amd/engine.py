@@ -275,11 +275,13 @@ class Job(object):
     prints and the block's (pre-filtered, tested, printed) counts.  Up to self.depth blocks may be in flight; collect() returns them in order.
     Everything a submitted block points at (rows, counts, names) is kept alive here until it has been collected."""
 
-    def __init__(self, engine, lmm, print_filtered=False, lineage_labels=None, lineage_per_variant=False, patterns=False, sample_names=None):
+    def __init__(self, engine, lmm, print_filtered=False, lineage_labels=None, lineage_per_variant=False, patterns=False, sample_names=None,
+                 pattern_count=False):
         """lineage_labels: the lineage column of the output (sh_job_set_lineage; the engine's lineage_setup must have run): fixed effects fit
         every printed row, the LMM one variant per block -- its last -- as pyseer/lmm.py:209-213 does, unless lineage_per_variant.
         patterns: hash_pattern of every tested variant, on the device (patterns() after each collect).  sample_names: the run's samples in the
-        engine's order -- printed rows carry their two sample lists (--print-samples), names sorted as the reference sorts them."""
+        engine's order -- printed rows carry their two sample lists (--print-samples), names sorted as the reference sorts them.
+        pattern_count: every tested variant's row goes into the engine's PatternSet (which must be open), with or without patterns."""
         self._lib = engine._lib
         self._eng = engine
         h = self._lib.sh_job_open(engine._h, int(bool(lmm)), int(bool(print_filtered)))
@@ -296,6 +298,11 @@ class Job(object):
         self._pat = bool(patterns)
         if patterns:
             _abi.check(self._lib.sh_job_set_patterns(self._h, 1))
+        if pattern_count:
+            rc = self._lib.sh_job_set_pattern_count(self._h, 1)
+            if rc:
+                self._lib.sh_job_close(self._h); self._h = None
+                _abi.check(rc)
         if sample_names is not None:
             enc = [str(x).encode() for x in sample_names]
             off = np.zeros(len(enc) + 1, dtype=np.int64)
@@ -372,4 +379,64 @@ class Job(object):
             pass
 
 
-__all__ = ["Engine", "Job", "pack_variants", "row_bytes_for"]
+class PatternSet(object):
+    """The run-wide set of distinct presence patterns of one engine (include/seerhip.h sh_patset_*): what scripts/count_patterns.py of the
+    reference counts with `sort -u | wc -l` over the --output-patterns file, kept on the device while the run goes.  One per engine at a time."""
+
+    def __init__(self, engine, initial_slots=0):
+        self._lib = engine._lib
+        self._eng = engine
+        _abi.check(self._lib.sh_patset_begin(engine._h, int(initial_slots)))
+        self._open = True
+
+    def add_rows(self, bits):
+        """bits (V, row_bytes) uint8 packed rows (pack_variants): every row is inserted."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        if bits.shape[0]:
+            _abi.check(self._lib.sh_patset_add_rows(self._eng._h, bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], bits.shape[0]))
+
+    def add_rows_dev(self, bits_t):
+        """The same for a (V, row_bytes) uint8 tensor on the engine's device."""
+        V, rb = bits_t.shape
+        _abi.check(self._lib.sh_patset_add_rows_dev(self._eng._h, C.c_void_p(bits_t.data_ptr()), rb, V))
+
+    def add_keys(self, keys):
+        """keys (n, 2) uint64 -- or n 16-byte digests as (n, 16) uint8."""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype == np.uint8:
+            keys = keys.reshape(-1, 16).view(np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        if keys.shape[0]:
+            _abi.check(self._lib.sh_patset_add_keys(self._eng._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)), keys.shape[0]))
+
+    def info(self):
+        """-> (distinct keys, slots, growths), after every insert queued so far"""
+        d = C.c_int64(); s = C.c_int64(); g = C.c_int64()
+        _abi.check(self._lib.sh_patset_count(self._eng._h, C.byref(d), C.byref(s), C.byref(g)))
+        return d.value, s.value, g.value
+
+    def count(self):
+        return self.info()[0]
+
+    def close(self):
+        if getattr(self, "_open", False) and getattr(self._eng, "_h", None):
+            self._lib.sh_patset_end(self._eng._h)
+        self._open = False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hash_rows(bits, n_samples):
+    """The (V, 2) uint64 keys the device gives the packed rows `bits` (sh_patset_hash_rows; host only)."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    keys = np.empty((bits.shape[0], 2), dtype=np.uint64)
+    _abi.check(_abi.load().sh_patset_hash_rows(bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], bits.shape[0], int(n_samples),
+                                               keys.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return keys
+
+
+__all__ = ["Engine", "Job", "PatternSet", "hash_rows", "pack_variants", "row_bytes_for"]
