@@ -198,7 +198,12 @@ int sh_get_lanes(sh_ctx *ctx);
  * Lineage effect (replaces pyseer/model.py:151 fit_lineage_effect): logistic regression of each VARIANT on
  * [1, lin, cov]; lin: n x l row-major (MDS components or cluster indicators, pyseer/__main__.py:417-432), cov: n x j
  * (or NULL, j = 0).  max_lineage[v] = argmax_j |beta_j|/bse_j over the l lineage columns, -1 = None (separation or
- * singular, model.py:193-197).  1 + l + j <= 16 in this build.
+ * singular, model.py:193-197).  1 + l + j <= 50 through the dense kernels (registers up to 16, run-time width above).  A design of
+ * cluster indicators and nothing else -- j = 0, every entry of lin exactly 0 or 1, at most one 1 per row, at least one row without
+ * (the reference cluster, whose column the command line dropped) -- needs no dense Hessian: the count kernel fits it from each
+ * cluster's carrier count, for any l up to 1023 (an empty column is legal: every variant answers -1, as the reference does).  It runs
+ * where the dense kernels stop (1 + l > 50); SEERHIP_ROUTE lin_counts=1 takes every such design through it, lin_counts=0 none.  Wider
+ * designs with covariates or with columns that are not cluster indicators are refused, and the message says which.
  * ------------------------------------------------------------------------------------------- */
 int sh_lineage_setup(sh_ctx *ctx, const double *lin, int l, const double *cov, int j);
 int sh_lineage_batch(sh_ctx *ctx, const uint8_t *bits, int64_t row_bytes, int64_t V, int32_t *max_lineage);

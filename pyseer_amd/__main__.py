@@ -7,7 +7,8 @@ end-of-run counters.  Variants are parsed in blocks of --block_size, packed, and
 printed in the reference's order (fixed effects: input order; LMM: within a block the filtered variants first, then the
 tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 
---lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 16).
+--lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 50; --lineage-clusters
+without covariates: up to 1023 clusters).
 
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
 reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or

@@ -161,6 +161,7 @@ struct sh_ctx {
     // ---- optional timing of the dominant kernel (sh_set_timing / sh_get_timing)
     int timing = 0;
     int lin_tab = 1;                                  // 0 would be the per-sample k_lmm_linear instead of the nibble tables
+    int lin_counts = -1;                              // SEERHIP_ROUTE lin_counts: -1 unset, 1 / 0 (sh_lineage_setup)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
     // ---- pattern de-duplication (sh_set_dedup)
     int dedup = 0; int64_t dd_cap = 0, dd_capV = 0, dd_last_unique = -1;
@@ -575,6 +576,7 @@ sh_ctx *sh_create(int device, int n_samples)
     if (const char *rv = sh_route("ragged")) c->ragged = std::atoi(rv);
     if (const char *lv = sh_route("lanes")) c->n_lanes = std::max(1, std::min(8, std::atoi(lv)));
     if (const char *ac = sh_route("afcompact")) c->af_compact = std::atoi(ac);
+    if (const char *lc = sh_route("lin_counts")) c->lin_counts = std::atoi(lc) != 0;
     c->NT = (n_samples + 255) / 256; c->Np = c->NT * 256;
     c->NB64 = (n_samples + 63) / 64; c->NB64p = c->NT * 4;
     return c;

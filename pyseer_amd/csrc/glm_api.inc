@@ -26,6 +26,7 @@ extern "C" int shk_firth_fastw_layout(int Q, int *t2h, int *t3h, int *rs, int *r
 extern "C" hipError_t shk_firth_fastw_launch(hipStream_t, int, int64_t, const uint64_t *, int64_t, GlmParams, double *, int *, int *, int *, int64_t,
                                              const int *, const int *, int *, int *, int *, int *, const uint16_t *, const float *, float *, int64_t);
 extern "C" hipError_t shk_glm_lineage(hipStream_t, int, const uint64_t *, int64_t, int64_t, int, int, const double *, int, int *, LinList);
+extern "C" hipError_t shk_glm_lineage_counts(hipStream_t, const uint64_t *, int64_t, int64_t, int, int, const uint16_t *, const int *, int, int *, LinList);
 struct GlmState {
     bool ready = false;
     int q = 0;
@@ -34,6 +35,8 @@ struct GlmState {
     double *d_y = nullptr, *d_W = nullptr, *d_yc = nullptr, *d_ZtZ = nullptr, *d_Zty = nullptr;
     uint64_t *d_y1 = nullptr, *d_y0 = nullptr;
     double *d_Xlin = nullptr; int lin_pc = 0, lin_n = 0; int *d_lin_out = nullptr; int64_t cap_lin = 0;
+    // the count route (k_glm_lineage_counts): every sample's cluster (0: the reference cluster, in no column) and the clusters' sizes [lin_n + 1]
+    uint16_t *d_lin_cof = nullptr; int *d_lin_nc = nullptr; bool lin_by_counts = false;
     double *d_bw = nullptr; int *d_state = nullptr, *d_slist = nullptr; int bw_q = -1;
     int *d_flist = nullptr, *d_fcount = nullptr, *d_plist = nullptr; int64_t cap_list = 0;   // d_fcount[0] firth, [1] pinv, [2] slow-Newton
     // Firth state machine (k_firth_init/eval/step): per-slot state, the work lists (eval, next eval, step, hand-off, fp64 step), their counters [0..4]
@@ -55,10 +58,17 @@ struct GlmState {
     int ff_first32 = 2;                // one-pass Firth: the first passes in single precision (SEERHIP_ROUTE firth_first32, read at set-up)
     int *d_tile_list = nullptr;        // (a list argument of shk_glm_launch that no kernel uses any more)
 };
+// fit_lineage_effect of the rows in T on the route sh_lineage_setup chose
+static hipError_t glm_lineage_launch(const GlmState &g, hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, int *out, LinList L)
+{
+    if (g.lin_by_counts) return shk_glm_lineage_counts(st, T, Vpad, V, N, NB64, g.d_lin_cof, g.d_lin_nc, g.lin_n, out, L);
+    if (g.lin_pc > 16) return shk_glm_wide_lineage(st, T, Vpad, V, N, NB64, g.d_Xlin, g.lin_pc, g.lin_n, out, L);
+    return shk_glm_lineage(st, g.lin_pc, T, Vpad, V, N, NB64, g.d_Xlin, g.lin_n, out, L);
+}
 static void glm_free(GlmState *g)
 {
     hipFree(g->d_Ws); hipFree(g->d_wstd); hipFree(g->d_Wf); hipFree(g->d_zz); hipFree(g->d_zz16); hipFree(g->d_zl16); hipFree(g->d_olstab); hipFree(g->d_y); hipFree(g->d_W); hipFree(g->d_yc); hipFree(g->d_ZtZ); hipFree(g->d_Zty); hipFree(g->d_y1); hipFree(g->d_y0);
-    hipFree(g->d_bw); hipFree(g->d_state); hipFree(g->d_slist); hipFree(g->d_Xlin); hipFree(g->d_lin_out); hipFree(g->d_flist); hipFree(g->d_fcount); hipFree(g->d_plist);
+    hipFree(g->d_bw); hipFree(g->d_state); hipFree(g->d_slist); hipFree(g->d_Xlin); hipFree(g->d_lin_out); hipFree(g->d_lin_cof); hipFree(g->d_lin_nc); hipFree(g->d_flist); hipFree(g->d_fcount); hipFree(g->d_plist);
     hipFree(g->d_fst); hipFree(g->d_fmeta); hipFree(g->d_fl[0]); hipFree(g->d_fl[1]); hipFree(g->d_fl[2]); hipFree(g->d_fl[3]); hipFree(g->d_fl[4]); hipFree(g->d_fcnt); hipFree(g->d_dbg); hipFree(g->d_tile_list); hipFree(g->d_w0); hipFree(g->d_a0); hipFree(g->d_bdi8); hipFree(g->d_bdscale); hipFree(g->d_chord); hipFree(g->d_bdtab); hipFree(g->d_b1); hipFree(g->d_pk); hipFree(g->d_rec); hipFree(g->d_rec_o); hipFree(g->d_rec_f); hipFree(g->d_rec_pf); hipFree(g->d_ff_tab); hipFree(g->d_ff_rec); hipFree(g->d_ff_inull); hipFree(g->d_ff_rec32); hipFree(g->d_ffw_tab); hipFree(g->d_ffw_rec); hipFree(g->d_ffw_ws);
     *g = GlmState();
 }

@@ -744,18 +744,53 @@ int sh_glm_info(sh_ctx *c, int64_t *firth_routed, int64_t *pinv_routed)
 int sh_lineage_setup(sh_ctx *c, const double *lin, int l, const double *cov, int j)
 {
     if (!c || !lin || l < 1 || j < 0 || (j > 0 && !cov)) return fail(SH_EINVAL, "bad argument");
-    const int PC = 1 + l + j;
-    if (PC > 50) return fail(SH_EINVAL, "1 + lineages + covariates must be <= 50 in this build");
+    const int PC = 1 + l + j, N = c->N;
+    // The count route (k_glm_lineage_counts): a design of disjoint cluster indicators and nothing else -- every entry exactly 0 or 1, at most
+    // one 1 per row, no covariates, somebody in no column (the reference cluster, whose column the command line dropped).  An empty column
+    // is legal (every variant answers None, as the reference does).
+    const std::string head = "1 + lineages + covariates must be <= 50 in this build unless the design is cluster indicators without covariates: ";
+    if (PC > 50) {
+        if (j > 0) return fail(SH_EINVAL, head + "this one has covariates");
+        if (l > LIN_COUNTS_MAX) return fail(SH_EINVAL, head + "more than LIN_COUNTS_MAX = " + std::to_string(LIN_COUNTS_MAX) + " clusters");
+        if (c->lin_counts == 0) return fail(SH_EINVAL, head + "and SEERHIP_ROUTE lin_counts=0 keeps it off the count kernel");
+    }
+    // (the design is only looked through where the count route can be taken at all)
+    bool by_counts = j == 0 && l <= LIN_COUNTS_MAX && c->lin_counts != 0 && (c->lin_counts == 1 || PC > 50);
+    std::vector<uint16_t> cof;
+    std::vector<int> nc;
+    if (by_counts) {
+        cof.assign((size_t)N, 0); nc.assign((size_t)l + 1, 0);
+        bool indicators = true;
+        for (int i = 0; i < N && indicators; ++i)
+            for (int a = 0; a < l; ++a) {
+                const double z = lin[(size_t)i * l + a];
+                if (z == 0.0) continue;
+                if (z != 1.0 || cof[i] != 0) { indicators = false; break; }
+                cof[i] = (uint16_t)(a + 1);                      // (l <= LIN_COUNTS_MAX < 65536)
+            }
+        if (indicators) for (int i = 0; i < N; ++i) ++nc[cof[i]];
+        by_counts = indicators && nc[0] > 0;
+        if (PC > 50 && !indicators) return fail(SH_EINVAL, head + "its lineage columns are not the indicators of disjoint clusters");
+        if (PC > 50 && !by_counts) return fail(SH_EINVAL, head + "no sample is left for the reference cluster (every row has a 1)");
+    }
     HIPCHK(hipSetDevice(c->device));
     GlmState &g = c->glm;
-    const int N = c->N;
+    hipFree(g.d_lin_cof); g.d_lin_cof = nullptr; hipFree(g.d_lin_nc); g.d_lin_nc = nullptr; g.lin_by_counts = false;
+    hipFree(g.d_Xlin); g.d_Xlin = nullptr; g.lin_n = 0; g.lin_pc = 0;
+    if (by_counts) {
+        HIPCHK(dmalloc(&g.d_lin_cof, cof.size())); HIPCHK(dmalloc(&g.d_lin_nc, nc.size()));
+        HIPCHK(hipMemcpyAsync(g.d_lin_cof, cof.data(), sizeof(uint16_t) * cof.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(g.d_lin_nc, nc.data(), sizeof(int) * nc.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        g.lin_by_counts = true;
+        if (PC > 50) { g.lin_pc = PC; g.lin_n = l; return SH_OK; }     // (narrower designs keep the dense design as well)
+    }
     std::vector<double> X((size_t)N * PC);
     for (int i = 0; i < N; ++i) {                    // [1, lin, c] as model.py:172-179
         X[(size_t)i * PC] = 1.0;
         for (int a = 0; a < l; ++a) X[(size_t)i * PC + 1 + a] = lin[(size_t)i * l + a];
         for (int a = 0; a < j; ++a) X[(size_t)i * PC + 1 + l + a] = cov[(size_t)i * j + a];
     }
-    hipFree(g.d_Xlin); g.d_Xlin = nullptr;
     HIPCHK(dmalloc(&g.d_Xlin, X.size()));
     HIPCHK(hipMemcpyAsync(g.d_Xlin, X.data(), sizeof(double) * X.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -766,7 +801,7 @@ int sh_lineage_setup(sh_ctx *c, const double *lin, int l, const double *cov, int
 // max_lineage[v] = index of the most significant lineage for variant v, or -1 (None)
 int sh_lineage_batch(sh_ctx *c, const uint8_t *bits, int64_t row_bytes, int64_t V, int32_t *max_lineage)
 {
-    if (!c || !c->glm.d_Xlin) return fail(SH_EINVAL, "sh_lineage_setup has not run");
+    if (!c || !c->glm.lin_n) return fail(SH_EINVAL, "sh_lineage_setup has not run");
     if (V <= 0) return SH_OK;
     if (!bits || !max_lineage) return fail(SH_EINVAL, "null argument");
     if (row_bytes * 8 < c->N) return fail(SH_ESHAPE, "row_bytes*8 < n_samples");
@@ -781,8 +816,7 @@ int sh_lineage_batch(sh_ctx *c, const uint8_t *bits, int64_t row_bytes, int64_t 
         if (Vpad > g.cap_lin) { hipFree(g.d_lin_out); g.d_lin_out = nullptr; HIPCHK(dmalloc(&g.d_lin_out, Vpad)); g.cap_lin = Vpad; }
         HIPCHK(hipMemcpyAsync(c->d_bits, bits + s * row_bytes, n * row_bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(shk_repack_bits(c->stream, c->d_bits, row_bytes, n, Vpad, c->N, c->NB64p, c->d_T, nullptr));
-        if (g.lin_pc > 16) HIPCHK(shk_glm_wide_lineage(c->stream, c->d_T, Vpad, n, c->N, c->NB64, g.d_Xlin, g.lin_pc, g.lin_n, g.d_lin_out, LinList{nullptr, nullptr, nullptr, 0}));
-        else HIPCHK(shk_glm_lineage(c->stream, g.lin_pc, c->d_T, Vpad, n, c->N, c->NB64, g.d_Xlin, g.lin_n, g.d_lin_out, LinList{nullptr, nullptr, nullptr, 0}));
+        HIPCHK(glm_lineage_launch(g, c->stream, c->d_T, Vpad, n, c->N, c->NB64, g.d_lin_out, LinList{nullptr, nullptr, nullptr, 0}));
         HIPCHK(hipMemcpyAsync(max_lineage + s, g.d_lin_out, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }

@@ -153,14 +153,12 @@ static int job_compute_on(sh_job *j, JobSlot &s, sh_ctx *k)
         const GlmState &pg = j->c->glm;
         if (j->lin_mode == 1) {
             const LinList L{s.d_sel, s.d_hdr, s.d_flags, j->lmm ? 2 : 1};
-            if (pg.lin_pc > 16) HIPCHK(shk_glm_wide_lineage(k->stream, k->d_T, Vpad, s.V, k->N, k->NB64, pg.d_Xlin, pg.lin_pc, pg.lin_n, slot_lin(s), L));
-            else HIPCHK(shk_glm_lineage(k->stream, pg.lin_pc, k->d_T, Vpad, s.V, k->N, k->NB64, pg.d_Xlin, pg.lin_n, slot_lin(s), L));
+            HIPCHK(glm_lineage_launch(pg, k->stream, k->d_T, Vpad, s.V, k->N, k->NB64, slot_lin(s), L));
         } else {
             HIPCHK(shk_repack_bits(k->stream, s.d_bits + (s.V - 1) * s.row_bytes, s.row_bytes, 1, 256, k->N, k->NB64p, s.d_T1, nullptr));
             const LinList L{nullptr, nullptr, nullptr, 0};
             int *one = (int *)(slot_hdr(s) + 4);
-            if (pg.lin_pc > 16) HIPCHK(shk_glm_wide_lineage(k->stream, s.d_T1, 256, 1, k->N, k->NB64, pg.d_Xlin, pg.lin_pc, pg.lin_n, one, L));
-            else HIPCHK(shk_glm_lineage(k->stream, pg.lin_pc, s.d_T1, 256, 1, k->N, k->NB64, pg.d_Xlin, pg.lin_n, one, L));
+            HIPCHK(glm_lineage_launch(pg, k->stream, s.d_T1, 256, 1, k->N, k->NB64, one, L));
         }
     }
     HIPCHK(hipEventRecord(s.ev_done, k->stream));
@@ -243,7 +241,7 @@ int sh_job_set_samples(sh_job *j, const char *names, const int64_t *name_off, co
 int sh_job_set_lineage(sh_job *j, const char *const *labels, int n_labels, int per_variant)
 {
     if (!j || !labels || n_labels < 1) return fail(SH_EINVAL, "sh_job_set_lineage: bad argument");
-    if (!j->c->glm.d_Xlin) return fail(SH_EINVAL, "sh_job_set_lineage: sh_lineage_setup has not run on the job's context");
+    if (!j->c->glm.lin_n) return fail(SH_EINVAL, "sh_job_set_lineage: sh_lineage_setup has not run on the job's context");
     if (n_labels != j->c->glm.lin_n) return fail(SH_EINVAL, "sh_job_set_lineage: one label per lineage column of sh_lineage_setup");
     if (j->n_submitted != j->n_collected) return fail(SH_EINVAL, "sh_job_set_lineage: blocks are in flight");
     j->lin_labels.assign(labels, labels + n_labels);

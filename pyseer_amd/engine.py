@@ -200,7 +200,9 @@ class Engine(object):
 
     # ---- lineage effect ------------------------------------------------------------------------
     def lineage_setup(self, lin, cov=None):
-        """lin (n, l): MDS components or cluster indicators; cov (n, j) or None (model.py:151-199)."""
+        """lin (n, l): MDS components or cluster indicators; cov (n, j) or None (model.py:151-199).  1 + l + j <= 50, or cluster indicators
+        without covariates (every entry 0 or 1, at most one 1 per row, some row without): up to 1023 columns, fitted from the clusters'
+        carrier counts (SEERHIP_ROUTE lin_counts=1 / 0: every such design / none)."""
         lin = np.asarray(lin, dtype=np.float64)
         if lin.ndim == 1:
             lin = lin.reshape(-1, 1)
