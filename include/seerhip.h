@@ -95,7 +95,11 @@ int     sh_set_timing(sh_ctx *ctx, int on);
 int     sh_get_timing(sh_ctx *ctx, double *total_ms, int64_t *launches);
 /* Pattern de-duplication (pyseer/input.py:710 hash_pattern, scripts/count_patterns.py): when on, every later
  * *_batch / *_batch_dev call tests each DISTINCT packed row once (exact row comparison, the hash only finds candidates) and fans
- * the result out to all variants that share it.  Outputs are unchanged.  Costs one stream synchronisation per batch. */
+ * the result out to all variants that share it.  Outputs are unchanged.  Costs one stream synchronisation per batch.
+ * sh_dedup_info: the number of rows the last batch (its last chunk) actually tested.  That is the number of distinct rows unless two
+ * different rows share all 64 bits of the hash: the hash then belongs to the one with the lowest index, and the other row -- and every
+ * duplicate of it, each on its own -- is tested as well.  So the count is an upper bound of the number of distinct patterns, and equal to
+ * it for all practical input (tests/test_dedup_collisions_gpu.py constructs the exception). */
 int     sh_set_dedup(sh_ctx *ctx, int on);
 int     sh_dedup_info(sh_ctx *ctx, int64_t *unique_last_batch);
 /* AF filter of the variant stream (pyseer/input.py:608,693): keep min_af <= count/n <= max_af (inclusive);

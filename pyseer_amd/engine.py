@@ -67,6 +67,7 @@ class Engine(object):
         _abi.check(self._lib.sh_set_dedup(self._h, int(bool(on))))
 
     def dedup_info(self):
+        """Rows the last batch tested: the number of distinct patterns, or more when different rows share a 64-bit hash (sh_dedup_info)."""
         n = C.c_int64()
         _abi.check(self._lib.sh_dedup_info(self._h, C.byref(n)))
         return n.value
