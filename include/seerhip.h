@@ -374,6 +374,9 @@ int     sh_patset_hash_rows(const uint8_t *bits, int64_t row_bytes, int64_t V, i
  * its nine fixed columns parsed on the host; the sample columns go to the device as they stand and k_vcf_gt_pack reduces every sample's
  * GT to present / missing / absent.  Bound to a context because it uses its device and stream; ctx == NULL selects the host restatement of
  * the kernel (measurements, and checks where there is no device) -- the command line never passes NULL.
+ * BCF 2.1 / 2.2 comes through the same entry points: the decoded stream is sniffed ("BCF\2"), records are framed by their length words,
+ * the shared block gives the name, the skip reason, POS and len(REF), and only the GT vector (n_sample x L bytes; int16 / int32 narrowed
+ * on the host) goes to the device, where k_bcf_gt_pack reduces it by the same rule.  BCF1 and minor versions above 2 are refused.
  *   sh_vcf_next: up to max_records records -> per record the skip reason (0 kept, 1 more than one ALT, 2 FILTER neither empty nor PASS;
  *   skipped records have rows of zeros), POS, len(REF), the contig's id (sh_vcf_contig), and two packed rows over sample_names in the
  *   engine's layout (LSB first, row_bytes as sh_lmm_batch): `present` and `missing` (a sample is never in both) with their popcounts.
@@ -391,6 +394,8 @@ int64_t     sh_vcf_next(sh_vcf *r, int64_t max_records, int32_t *skip, int64_t *
 int64_t     sh_vcf_names(sh_vcf *r, const char **blob, const int64_t **name_off);
 /* mode: 0 plain, 1 gzip, 2 BGZF; the sample columns of the header; contigs met so far */
 int         sh_vcf_info(sh_vcf *r, int *mode, int *n_cols, int *n_contigs);
+/* what the decoded bytes hold: 0 VCF text, 1 BCF (sniffed when the file is opened, whatever its name) */
+int         sh_vcf_format(sh_vcf *r);
 const char *sh_vcf_contig(sh_vcf *r, int id);
 /* bytes of sample columns handed to the tokeniser, records delivered, kernel launches so far */
 int         sh_vcf_stats(sh_vcf *r, int64_t *sample_bytes, int64_t *records, int64_t *launches);

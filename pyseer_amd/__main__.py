@@ -13,7 +13,10 @@ without covariates: up to 1023 clusters).
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
 reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or
 line by line (--python-reader; also with --gpus, and for a header that names a sample twice).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
-and --pres and --python-reader line by line.  Not supported (out of scope): --wg rf / blup, BCF, and --gpus / the packed cache with a VCF.
+and --pres and --python-reader line by line.  BCF 2.1 / 2.2 is read through --vcf wherever VCF text is (sniffed from the decoded bytes, whatever the file is called): natively with each
+record's GT vector reduced on the device (k_bcf_gt_pack), or by the Python reader (--python-reader, input.BcfFile).
+Not supported (out of scope): --wg rf / blup, --gpus / the packed cache with a VCF or BCF, and around BCF: .csi / .tbi indexes (burden
+regions stay one pass over the file), INFO and FORMAT fields other than GT, BCF1 and minor versions above 2 (refused by name), writing BCF.
 """
 import argparse
 import os

@@ -110,6 +110,7 @@ SIGNATURES = {
                                 C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sh_vcf_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "sh_vcf_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sh_vcf_format": (C.c_int, [C.c_void_p]),
     "sh_vcf_contig": (C.c_char_p, [C.c_void_p, C.c_int]),
     "sh_vcf_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sh_burden_fold": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, c_u8p, c_u8p,

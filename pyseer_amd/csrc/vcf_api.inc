@@ -3,6 +3,8 @@
 // the sample columns of a sub-batch are copied as they stand into one of two pinned slabs (each record at a 16-byte aligned offset), go to the
 // device with the records' offsets, and k_vcf_gt_pack writes their present / missing rows; while that runs, the host decodes and frames the
 // next sub-batch into the other slab.  A record longer than a slab makes the slabs grow.  The rows of the whole call come back at its end.
+// BCF takes the same pump: what a record puts into the slab is its GT vector alone (n_cols x L bytes, csrc/vcf_reader.cpp "BCF"), and the
+// kernel is k_bcf_gt_pack.
 
 struct sh_vcf {
     sh_ctx *ctx = nullptr;                                 // nullptr: the host tokeniser (shvcf::host_gt_pack) stands in for the kernel
@@ -107,7 +109,7 @@ static int vcf_launch(sh_vcf *r, int slot, size_t used, int64_t nrec, int64_t ro
     sh_ctx *c = r->ctx;
     if (used) HIPCHK(hipMemcpyAsync(r->d_bytes[slot], r->h_bytes[slot], used, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(r->d_recs[slot], r->h_recs[slot], sizeof(ShVcfRec) * (size_t)nrec, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(shk_vcf_gt_pack(c->stream, r->d_bytes[slot], r->d_recs[slot], nrec, r->d_col2idx, r->n_cols, r->row_words,
+    HIPCHK((shvcf::format(r->rd) ? shk_bcf_gt_pack : shk_vcf_gt_pack)(c->stream, r->d_bytes[slot], r->d_recs[slot], nrec, r->d_col2idx, r->n_cols, r->row_words,
                            r->d_present + (size_t)row0 * r->row_words, r->d_missing + (size_t)row0 * r->row_words, r->d_np + row0, r->d_nm + row0));
     HIPCHK(hipEventRecord(r->ev[slot], c->stream));
     r->ev_used[slot] = true;
@@ -122,6 +124,7 @@ int64_t sh_vcf_next(sh_vcf *r, int64_t max_records, int32_t *skip, int64_t *pos,
     if (row_bytes != (int64_t)r->row_words * 4) { fail(SH_ESHAPE, "row_bytes is not that of the reader's sample count"); return -1; }
     if (max_records < 1) return 0;
     sh_ctx *c = r->ctx;
+    const bool bcf = shvcf::format(r->rd) != 0;
     if (c) {
         if (hipSetDevice(c->device) != hipSuccess) { fail(SH_EHIP, "hipSetDevice"); return -1; }
         if (vcf_ensure_rows(r, max_records) != SH_OK) return -1;
@@ -157,6 +160,7 @@ int64_t sh_vcf_next(sh_vcf *r, int64_t max_records, int32_t *skip, int64_t *pos,
                 if (vcf_alloc_slabs(r, need * 2) != SH_OK) return -1;
             }
             ShVcfRec d; d.off = used; d.len = send ? (uint32_t)rec.samp_len : 0u; d.gt = rec.skip != shvcf::KEPT ? -2 : rec.gt;
+            if (bcf) d.len = send ? (uint32_t)rec.gt : 0u;                // (the GT vector's values per sample; its bytes are n_cols times that)
             if (c) {
                 if (send) { memcpy(r->h_bytes[slot] + used, rec.samp, rec.samp_len); memset(r->h_bytes[slot] + used + rec.samp_len, 0, need - rec.samp_len); }
                 r->h_recs[slot][nrec] = d;
@@ -180,8 +184,9 @@ int64_t sh_vcf_next(sh_vcf *r, int64_t max_records, int32_t *skip, int64_t *pos,
             memset(present + (size_t)done * row_bytes, 0, (size_t)nrec * row_bytes); memset(missing + (size_t)done * row_bytes, 0, (size_t)nrec * row_bytes);
             const std::function<void(int64_t)> fn = [&](int64_t k) {
                 const ShVcfRec &d = host_recs[(size_t)k];
-                shvcf::host_gt_pack(r->host_bytes.data() + d.off, d.len, d.gt, c2i, r->n_cols, (uint32_t *)(present + (size_t)(done + k) * row_bytes),
-                                    (uint32_t *)(missing + (size_t)(done + k) * row_bytes), r->row_words, n_present + done + k, n_missing + done + k);
+                uint32_t *const P = (uint32_t *)(present + (size_t)(done + k) * row_bytes), *const M = (uint32_t *)(missing + (size_t)(done + k) * row_bytes);
+                if (bcf) shvcf::host_bcf_pack(r->host_bytes.data() + d.off, d.len, d.gt, c2i, r->n_cols, P, M, r->row_words, n_present + done + k, n_missing + done + k);
+                else shvcf::host_gt_pack(r->host_bytes.data() + d.off, d.len, d.gt, c2i, r->n_cols, P, M, r->row_words, n_present + done + k, n_missing + done + k);
             };
             shost::pool().run(nrec, 1, fn, shost::ST_READER_PARSE);
             r->stat_bytes += (int64_t)used;
@@ -216,6 +221,8 @@ int sh_vcf_info(sh_vcf *r, int *mode, int *n_cols, int *n_contigs)
     if (n_contigs) *n_contigs = shvcf::n_contigs(r->rd);
     return SH_OK;
 }
+
+int sh_vcf_format(sh_vcf *r) { return r ? shvcf::format(r->rd) : fail(SH_EINVAL, "null reader"); }
 
 const char *sh_vcf_contig(sh_vcf *r, int id) { return r ? shvcf::contig_name(r->rd, id) : ""; }
 

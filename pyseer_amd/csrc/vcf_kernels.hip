@@ -13,6 +13,11 @@
 // Columns the record does not have (a short line), and every column of a record whose FORMAT has no GT, are missing.  The two rows and
 // their popcounts leave with plain vector stores.  k_burden_fold: OR of the present rows of a burden variant's records, the missing row of
 // its last record, missing cleared where present (pyseer/input.py:383-407 + 455-503 on one dictionary).
+//
+// k_bcf_gt_pack: the same rows from BCF records.  A record's GT vector -- n_cols x L values in the int8 coding, (allele + 1) << 1 | phased,
+// 0x81 the end of a shorter vector, 0x80 the missing value -- lies in the batch buffer at a 16-byte aligned offset; nothing is tokenised.
+// One workgroup per record; a lane takes a column, consecutive lanes consecutive columns (L = 1: one byte, L = 2: one 16-bit load, else a
+// loop over L bytes), reduces it by the rule of vcf_gt_code and sets the bit as above.
 #include "common.h"
 #include "vcf_kernels.h"
 
@@ -127,6 +132,74 @@ __global__ __launch_bounds__(VCF_WG) void k_vcf_gt_pack(const uint8_t *__restric
     if (tid == 0) { n_present[blockIdx.x] = s_cnt[0]; n_missing[blockIdx.x] = s_cnt[1]; }
 }
 
+// the three-way code of one sample's L values (shvcf::bcf_gt_code, csrc/vcf_reader.cpp, is this function on the host)
+__device__ __forceinline__ int bcf_gt_step(const uint32_t b, int &last)
+{
+    if (b == 0x80u) { last = 2; return 0; }               // the type's missing value
+    const int allele = (int)(b >> 1) - 1;
+    if (allele >= 1) return 1;
+    last = allele == 0 ? 0 : 2;
+    return 0;
+}
+
+__global__ __launch_bounds__(VCF_WG) void k_bcf_gt_pack(const uint8_t *__restrict__ bytes, const ShVcfRec *__restrict__ recs,
+                                                        const int32_t *__restrict__ col2idx, const int n_cols, const int row_words,
+                                                        uint32_t *__restrict__ present, uint32_t *__restrict__ missing,
+                                                        int32_t *__restrict__ n_present, int32_t *__restrict__ n_missing)
+{
+    extern __shared__ uint32_t s_rows[];                  // [row_words] present, [row_words] missing
+    __shared__ int s_cnt[2];
+    const int tid = threadIdx.x;
+    const ShVcfRec r = recs[blockIdx.x];
+    uint32_t *P = s_rows, *M = s_rows + row_words;
+    for (int i = tid; i < 2 * row_words; i += VCF_WG) s_rows[i] = 0;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    if (r.gt >= -1) {                                     // (gt == -2: a skipped record, rows of zeros)
+        const uint8_t *__restrict__ b = bytes + r.off;
+        const uint32_t L = r.len;
+        for (int col = tid; col < n_cols; col += VCF_WG) {
+            const int idx = col2idx[col];
+            if (idx < 0) continue;
+            int code = 2, last = 2;                       // no GT in the record: every sample of the file is missing
+            if (r.gt >= 0) {
+                if (L == 1) {
+                    const uint32_t v = b[col];
+                    code = v == 0x81u ? 2 : (bcf_gt_step(v, last) ? 1 : last);
+                } else if (L == 2) {
+                    const uint32_t v = *(const uint16_t *)(b + 2 * (size_t)col), v0 = v & 0xffu, v1 = v >> 8;
+                    if (v0 == 0x81u) code = 2;
+                    else if (bcf_gt_step(v0, last)) code = 1;
+                    else code = v1 == 0x81u ? last : (bcf_gt_step(v1, last) ? 1 : last);
+                } else {
+                    const uint8_t *__restrict__ q = b + (size_t)col * L;
+                    bool hit = false;
+                    for (uint32_t j = 0; j < L; ++j) {
+                        const uint32_t v = q[j];
+                        if (v == 0x81u) break;
+                        if (bcf_gt_step(v, last)) { hit = true; break; }
+                    }
+                    code = hit ? 1 : last;
+                }
+            }
+            if (code == 1) atomicOr(&P[idx >> 5], 1u << (idx & 31));
+            else if (code == 2) atomicOr(&M[idx >> 5], 1u << (idx & 31));
+        }
+    }
+    __syncthreads();
+    int np = 0, nm = 0;
+    const size_t row0 = (size_t)blockIdx.x * (size_t)row_words;
+    for (int i = tid; i < row_words; i += VCF_WG) {
+        const uint32_t p = P[i], m = M[i] & ~p;
+        present[row0 + i] = p; missing[row0 + i] = m;
+        np += __popc(p); nm += __popc(m);
+    }
+    if (np) atomicAdd(&s_cnt[0], np);
+    if (nm) atomicAdd(&s_cnt[1], nm);
+    __syncthreads();
+    if (tid == 0) { n_present[blockIdx.x] = s_cnt[0]; n_missing[blockIdx.x] = s_cnt[1]; }
+}
+
 __global__ __launch_bounds__(VCF_WG) void k_burden_fold(const uint32_t *__restrict__ present, const uint32_t *__restrict__ missing, const int row_words,
                                                         const int64_t n_records, const int64_t *__restrict__ csr_off, const int32_t *__restrict__ csr_idx,
                                                         uint32_t *__restrict__ out_present, uint32_t *__restrict__ out_missing,
@@ -163,6 +236,15 @@ hipError_t shk_vcf_gt_pack(hipStream_t st, const uint8_t *bytes, const ShVcfRec 
 {
     if (n_records <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_vcf_gt_pack, dim3((unsigned)n_records), dim3(VCF_WG), shk_vcf_lds_bytes(row_words), st, bytes, recs, col2idx, n_cols, row_words,
+                       present, missing, n_present, n_missing);
+    return hipGetLastError();
+}
+
+hipError_t shk_bcf_gt_pack(hipStream_t st, const uint8_t *bytes, const ShVcfRec *recs, int64_t n_records, const int32_t *col2idx, int n_cols, int row_words,
+                           uint32_t *present, uint32_t *missing, int32_t *n_present, int32_t *n_missing)
+{
+    if (n_records <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bcf_gt_pack, dim3((unsigned)n_records), dim3(VCF_WG), shk_vcf_lds_bytes(row_words), st, bytes, recs, col2idx, n_cols, row_words,
                        present, missing, n_present, n_missing);
     return hipGetLastError();
 }

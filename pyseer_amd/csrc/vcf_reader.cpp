@@ -8,6 +8,9 @@
 //     nor holds PASS), POS, len(REF) (the span burden regions are matched against), where GT sits in FORMAT.
 // The sample columns -- ~99 % of the bytes: `0:186,0:186:99:0,1800` per sample -- are NOT tokenised here: next() hands them out as they
 // stand, and csrc/vcf_api.inc sends them to the device (k_vcf_gt_pack, csrc/vcf_kernels.hip).  No index file (.tbi / .csi) is read.
+// BCF 2.1 / 2.2 (the section "BCF" below) comes through the same container and window: the format is sniffed from the first decoded bytes,
+// records are framed by their two length words, the shared block gives what the nine columns give, and of the individual block only the GT
+// vector is handed out -- n_sample x L typed integers, which k_bcf_gt_pack reduces on the device.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -56,6 +59,9 @@ struct Reader {
     std::unordered_map<std::string, int> contig_id; std::vector<std::string> contigs;
     std::unordered_map<std::string, int> sample_idx;
     std::string name;
+    // BCF: 1 if the decoded stream is BCF2; records read so far; the dictionary index of GT (-1: not declared); index -> contig name
+    int format = 0; int64_t bcf_rec = 0; int bcf_gt_key = -1; std::unordered_map<int64_t, std::string> bcf_contigs;
+    std::vector<uint8_t> narrow;                          // a GT vector of int16 / int32 values in the int8 coding
     ~Reader() { if (map && map_len) munmap((void *)map, map_len); if (fd >= 0) ::close(fd); }
 };
 
@@ -160,6 +166,227 @@ static bool next_line(Reader *r, const uint8_t *&line, size_t &len, std::string 
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// BCF 2.1 / 2.2.  All integers little-endian.  File: "BCF" 2 minor | l_text u32 | header text (VCF header, NUL-terminated) | records.
+// Record: l_shared u32 | l_indiv u32 | shared: CHROM i32, POS i32 (0-based), rlen i32, QUAL f32, n_allele<<16|n_info u32, n_fmt<<24|n_sample
+// u32, ID, n_allele alleles (typed strings), FILTER (typed ints), INFO (not read) | individual: n_fmt x (key typed int, descriptor with the
+// per-sample count L, n_sample x L values).  A typed value starts with a descriptor byte: low 4 bits the type (0 void, 1 int8, 2 int16,
+// 3 int32, 5 float32, 7 char), high 4 bits the count, 15 = a typed integer with the count follows.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+
+// at least n unread bytes in the window; false when the stream ends before (or on error: err set)
+static bool ensure(Reader *r, size_t n, std::string &err)
+{
+    while (r->end - r->beg < n)
+        if (!fill(r, err)) return r->end - r->beg >= n;
+    return true;
+}
+
+static inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// ID and IDX of a `##KIND=<key=value,...>` line (values may be quoted); p: behind '<'.  false: the line has no ID
+static bool meta_id(const char *p, const char *const e, std::string &id, int64_t &idx)
+{
+    bool have = false;
+    idx = -1;
+    while (p < e && *p != '>') {
+        const char *k = p;
+        while (p < e && *p != '=' && *p != ',' && *p != '>') ++p;
+        const std::string key(k, p);
+        std::string val;
+        if (p < e && *p == '=') {
+            ++p;
+            if (p < e && *p == '"') {
+                ++p;
+                while (p < e && *p != '"') { if (*p == '\\' && p + 1 < e) ++p; val += *p++; }
+                if (p < e) ++p;
+            } else {
+                const char *v = p;
+                while (p < e && *p != ',' && *p != '>') ++p;
+                val.assign(v, p);
+            }
+        }
+        if (key == "ID") { id = val; have = true; }
+        else if (key == "IDX") { idx = -1; if (!val.empty() && val.size() < 10 && val.find_first_not_of("0123456789") == std::string::npos) idx = atoll(val.c_str()); }
+        if (p < e && *p == ',') ++p;
+    }
+    return have;
+}
+
+// the file head behind the sniffed "BCF": version, header text -> the dictionary's GT, the contigs, the sample columns
+static bool bcf_head(Reader *r, const char *path, std::string &err)
+{
+    if (!ensure(r, 9, err)) { if (err.empty()) err = std::string(path) + ": BCF: the file ends inside its head"; return false; }
+    const uint8_t *h = r->win.data() + r->beg;
+    if (h[3] == 4) { err = std::string(path) + " is BCF1 (BCF\\4), which is not read: BCF 2.1 and 2.2 are"; return false; }
+    if (h[3] != 2) { err = std::string(path) + ": BCF major version " + std::to_string((int)h[3]) + " is not read: BCF 2.1 and 2.2 are"; return false; }
+    if (h[4] != 1 && h[4] != 2) { err = std::string(path) + ": BCF minor version " + std::to_string((int)h[4]) + " is not read: BCF 2.1 and 2.2 are"; return false; }
+    const size_t l_text = le32(h + 5);
+    if (!ensure(r, 9 + l_text, err)) { if (err.empty()) err = std::string(path) + ": BCF: the file ends inside its header text"; return false; }
+    const char *t = (const char *)r->win.data() + r->beg + 9, *const te = t + l_text;
+    const char *const nul = (const char *)memchr(t, 0, l_text), *const end = nul ? nul : te;
+    std::unordered_map<std::string, int64_t> dict;
+    dict.emplace("PASS", 0);
+    int64_t n_contig = 0;
+    std::string id;
+    while (t < end) {
+        const char *nl = (const char *)memchr(t, '\n', (size_t)(end - t));
+        const char *le = nl ? nl : end;
+        const char *const next_t = nl ? nl + 1 : end;
+        if (le > t && le[-1] == '\r') --le;
+        const size_t len = (size_t)(le - t);
+        int64_t idx;
+        if (len >= 10 && memcmp(t, "##contig=<", 10) == 0) {
+            if (meta_id(t + 10, le, id, idx)) { r->bcf_contigs.emplace(idx >= 0 ? idx : n_contig, id); ++n_contig; }
+        } else if ((len >= 10 && memcmp(t, "##FILTER=<", 10) == 0) || (len >= 10 && memcmp(t, "##FORMAT=<", 10) == 0) || (len >= 8 && memcmp(t, "##INFO=<", 8) == 0)) {
+            if (meta_id(t + (t[2] == 'I' ? 8 : 10), le, id, idx) && !dict.count(id)) { const int64_t at = idx >= 0 ? idx : (int64_t)dict.size(); dict.emplace(id, at); }
+        } else if (len >= 6 && memcmp(t, "#CHROM", 6) == 0) {
+            int col = 0;
+            for (const char *p = t; p <= le;) {
+                const char *tab = (const char *)memchr(p, '\t', (size_t)(le - p));
+                if (!tab) tab = le;
+                if (col >= 9) {
+                    auto it = r->sample_idx.find(std::string(p, (size_t)(tab - p)));
+                    r->col2idx.push_back(it == r->sample_idx.end() ? -1 : it->second);
+                }
+                ++col; p = tab + 1;
+            }
+            r->have_header = true;
+        }
+        t = next_t;
+    }
+    if (!r->have_header) { err = std::string(path) + ": the BCF header text has no #CHROM line"; return false; }
+    auto gt = dict.find("GT");
+    r->bcf_gt_key = gt == dict.end() ? -1 : (int)gt->second;
+    r->beg += 9 + l_text; r->scan = r->beg;
+    r->format = 1;
+    return true;
+}
+
+struct Cur { const uint8_t *p, *e; };
+
+// a typed integer scalar (the count in a long descriptor; a FORMAT key)
+static bool typed_scalar(Cur &c, int64_t &v)
+{
+    if (c.p >= c.e) return false;
+    const uint8_t d = *c.p++;
+    const int t = d & 15;
+    if ((d >> 4) != 1 || t < 1 || t > 3) return false;
+    const size_t w = (size_t)1 << (t - 1);
+    if ((size_t)(c.e - c.p) < w) return false;
+    v = t == 1 ? (int64_t)(int8_t)c.p[0] : t == 2 ? (int64_t)(int16_t)(c.p[0] | (c.p[1] << 8)) : (int64_t)(int32_t)le32(c.p);
+    c.p += w;
+    return true;
+}
+
+static bool typed_desc(Cur &c, int &type, uint64_t &count)
+{
+    if (c.p >= c.e) return false;
+    const uint8_t d = *c.p++;
+    type = d & 15; count = d >> 4;
+    if (count == 15) { int64_t v; if (!typed_scalar(c, v) || v < 0) return false; count = (uint64_t)v; }
+    return true;
+}
+
+static inline size_t type_width(int type) { return type == 1 || type == 7 ? 1 : type == 2 ? 2 : type == 3 || type == 5 ? 4 : 0; }
+
+static bool typed_string(Cur &c, const uint8_t *&s, size_t &n)
+{
+    int type; uint64_t count;
+    if (!typed_desc(c, type, count)) return false;
+    if (type == 0) { s = c.p; n = 0; return true; }
+    if (type != 7 || (uint64_t)(c.e - c.p) < count) return false;
+    s = c.p; n = (size_t)count; c.p += count;
+    return true;
+}
+
+// int16 / int32 GT values in the int8 coding: the end-of-vector and the missing mark become int8's, an allele index int8 cannot hold (a kept
+// record has at most two alleles: none of its values needs more) stays a non-zero allele
+static void narrow_gt(uint8_t *dst, const uint8_t *src, size_t n, int width)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t v = width == 2 ? (uint32_t)(src[2 * i] | (src[2 * i + 1] << 8)) : le32(src + 4 * i);
+        const uint32_t eov = width == 2 ? 0x8001u : 0x80000001u, mis = width == 2 ? 0x8000u : 0x80000000u;
+        dst[i] = v == eov ? 0x81 : v == mis ? 0x80 : v < 0x80u ? (uint8_t)v : (uint8_t)(0x7e | (v & 1u));
+    }
+}
+
+static int bcf_next(Reader *r, Record &rec, std::string &err)
+{
+    if (!ensure(r, 8, err)) {
+        if (!err.empty()) return -1;
+        if (r->end == r->beg) return 0;
+        err = "BCF: the file ends inside the lengths of record " + std::to_string(r->bcf_rec + 1); return -1;
+    }
+    const int64_t no = ++r->bcf_rec;
+    const std::string where = "BCF: record " + std::to_string(no) + ": ";
+    const size_t l_shared = le32(r->win.data() + r->beg), l_indiv = le32(r->win.data() + r->beg + 4);
+    if (!ensure(r, 8 + l_shared + l_indiv, err)) { if (err.empty()) err = where + "the file ends inside it"; return -1; }
+    const uint8_t *const sh = r->win.data() + r->beg + 8;
+    r->beg += 8 + l_shared + l_indiv; r->scan = r->beg;
+    if (l_shared < 24) { err = where + "a shared block shorter than its fixed part"; return -1; }
+    const int64_t chrom = (int32_t)le32(sh), pos0 = (int32_t)le32(sh + 4);
+    const uint32_t n_allele = le32(sh + 16) >> 16, n_fmt = le32(sh + 20) >> 24, n_sample = le32(sh + 20) & 0xffffffu;
+    auto ct = r->bcf_contigs.find(chrom);
+    if (ct == r->bcf_contigs.end()) { err = where + "CHROM index " + std::to_string(chrom) + " names no ##contig line of the header"; return -1; }
+    if (n_sample != 0 && n_sample != (uint32_t)r->col2idx.size()) {
+        err = where + "n_sample is " + std::to_string(n_sample) + ", the header has " + std::to_string(r->col2idx.size()) + " sample columns"; return -1;
+    }
+    Cur c{sh + 24, sh + l_shared};
+    const uint8_t *s; size_t n;
+    if (!typed_string(c, s, n)) { err = where + "ID runs past the shared block"; return -1; }
+    const std::string &chrom_name = ct->second;
+    auto it = r->contig_id.find(chrom_name);
+    if (it == r->contig_id.end()) { it = r->contig_id.emplace(chrom_name, (int)r->contigs.size()).first; r->contigs.push_back(chrom_name); }
+    rec.contig = it->second;
+    rec.pos = pos0 + 1;
+    rec.ref_len = 0;
+    r->name.assign(chrom_name); r->name += '_'; r->name += std::to_string(pos0 + 1); r->name += '_';
+    for (uint32_t a = 0; a < n_allele; ++a) {
+        if (!typed_string(c, s, n)) { err = where + "an allele runs past the shared block"; return -1; }
+        if (a == 0) rec.ref_len = (int32_t)n;
+        if (a) r->name += a == 1 ? '_' : ',';              // (several ALTs: the text route's name carries ALT as it stands, commas included)
+        r->name.append((const char *)s, n);
+    }
+    rec.name = r->name.data(); rec.name_len = r->name.size();
+    int type; uint64_t count;
+    if (!typed_desc(c, type, count) || (type != 0 && (type > 3 || (uint64_t)(c.e - c.p) < count * type_width(type)))) { err = where + "FILTER runs past the shared block"; return -1; }
+    bool any = false, pass = false;
+    if (type != 0)
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint8_t *q = c.p + i * type_width(type);
+            const uint32_t v = type == 1 ? q[0] : type == 2 ? (uint32_t)(q[0] | (q[1] << 8)) : le32(q);
+            const uint32_t mis = type == 1 ? 0x80u : type == 2 ? 0x8000u : 0x80000000u;
+            if (v == mis || v == mis + 1) continue;       // (a missing entry names no filter)
+            any = true;
+            if (v == 0) pass = true;
+        }
+    rec.skip = n_allele > 2 ? MULTI : ((any && !pass) ? FILTERED : KEPT);
+    rec.gt = -1; rec.samp = sh + l_shared; rec.samp_len = 0;
+    if (rec.skip != KEPT || n_sample == 0) return 1;
+    // the individual block: every field before GT is skipped by its length
+    Cur d{sh + l_shared, sh + l_shared + l_indiv};
+    for (uint32_t f = 0; f < n_fmt; ++f) {
+        int64_t key;
+        if (!typed_scalar(d, key) || !typed_desc(d, type, count)) { err = where + "a FORMAT field runs past the individual block"; return -1; }
+        const size_t w = type_width(type);
+        if (type != 0 && w == 0) { err = where + "a FORMAT field of unknown type " + std::to_string(type); return -1; }
+        if (count > (uint64_t)1 << 31 || (uint64_t)(d.e - d.p) < count * w * n_sample) { err = where + "a FORMAT field runs past the individual block"; return -1; }
+        if (key == r->bcf_gt_key && r->bcf_gt_key >= 0) {
+            if (type == 0 || count == 0) break;           // an empty vector: every sample missing
+            if (type > 3) { err = where + "GT is not a vector of integers"; return -1; }
+            const size_t vals = (size_t)count * n_sample;
+            if (vals >= ((size_t)1 << 31)) { err = where + "a GT vector of 2 GB or more"; return -1; }
+            rec.gt = (int32_t)count; rec.samp_len = vals;
+            if (w == 1) rec.samp = d.p;
+            else { r->narrow.resize(vals); narrow_gt(r->narrow.data(), d.p, vals, (int)w); rec.samp = r->narrow.data(); }   // (the rare path)
+            break;
+        }
+        d.p += count * w * n_sample;
+    }
+    return 1;
+}
+
 Reader *open_file(const char *path, const char *const *sample_names, int n_samples, std::string &err)
 {
     std::unique_ptr<Reader> r(new Reader());
@@ -178,6 +405,12 @@ Reader *open_file(const char *path, const char *const *sample_names, int n_sampl
     if (r->mode == 2) r->pool.reset(new shost::ParPool(std::max(1, std::min(16, shost::per_stream_cpus(2)) - 1), shost::ST_READER_DECODE));
     if (r->map_len == 0) r->eof = true;
     for (int i = 0; i < n_samples; ++i) r->sample_idx.emplace(sample_names[i], i);
+    // BCF or text: the first decoded bytes tell ("BCF" + major version; a VCF starts with '#')
+    if (!ensure(r.get(), 5, err) && !err.empty()) return nullptr;
+    if (r->end - r->beg >= 4 && memcmp(r->win.data() + r->beg, "BCF", 3) == 0) {
+        if (!bcf_head(r.get(), path, err)) return nullptr;
+        return r.release();
+    }
     // the header: everything up to and including the #CHROM line
     const uint8_t *line; size_t len;
     while (!r->have_header) {
@@ -211,9 +444,11 @@ const int32_t *col_to_sample(const Reader *r) { return r->col2idx.data(); }
 int n_contigs(const Reader *r) { return (int)r->contigs.size(); }
 const char *contig_name(const Reader *r, int id) { return id >= 0 && id < (int)r->contigs.size() ? r->contigs[(size_t)id].c_str() : ""; }
 int mode(const Reader *r) { return r->mode; }
+int format(const Reader *r) { return r->format; }
 
 int next(Reader *r, Record &rec, std::string &err)
 {
+    if (r->format) return bcf_next(r, rec, err);
     const uint8_t *line; size_t len;
     do {
         if (!next_line(r, line, len, err)) return err.empty() ? 0 : -1;
@@ -307,6 +542,37 @@ void host_gt_pack(const uint8_t *samp, size_t len, int gt, const int32_t *col2id
     }
     if (gt >= -1)
         for (; col < n_cols; ++col) { const int idx = col2idx[col]; if (idx >= 0) missing[idx >> 5] |= 1u << (idx & 31); }
+    int np = 0, nm = 0;
+    for (int i = 0; i < row_words; ++i) { missing[i] &= ~present[i]; np += __builtin_popcount(present[i]); nm += __builtin_popcount(missing[i]); }
+    *n_present = np; *n_missing = nm;
+}
+
+// the three-way code of one sample's L GT values in the int8 coding (k_bcf_gt_pack's bcf_gt_code restated)
+static inline int bcf_gt_code(const uint8_t *p, const uint32_t L)
+{
+    int last = 2;
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint8_t b = p[j];
+        if (b == 0x81) break;                             // end of vector
+        if (b == 0x80) { last = 2; continue; }            // the type's missing value
+        const int allele = (b >> 1) - 1;
+        if (allele >= 1) return 1;
+        last = allele == 0 ? 0 : 2;
+    }
+    return last;
+}
+
+void host_bcf_pack(const uint8_t *gt, uint32_t L, int has_gt, const int32_t *col2idx, int n_cols, uint32_t *present, uint32_t *missing, int row_words,
+                   int32_t *n_present, int32_t *n_missing)
+{
+    if (has_gt >= -1)
+        for (int col = 0; col < n_cols; ++col) {
+            const int idx = col2idx[col];
+            if (idx < 0) continue;
+            const int code = has_gt >= 0 ? bcf_gt_code(gt + (size_t)col * L, L) : 2;
+            if (code == 1) present[idx >> 5] |= 1u << (idx & 31);
+            else if (code == 2) missing[idx >> 5] |= 1u << (idx & 31);
+        }
     int np = 0, nm = 0;
     for (int i = 0; i < row_words; ++i) { missing[i] &= ~present[i]; np += __builtin_popcount(present[i]); nm += __builtin_popcount(missing[i]); }
     *n_present = np; *n_missing = nm;

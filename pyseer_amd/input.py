@@ -5,13 +5,15 @@ fixed_effects_regression, input.py:608-620; load_var_block: (variants, variant_m
 callers keep working; `iter_packed_blocks` is the feed of the GPU driver: the same parsing, but presence goes straight
 into packed bit rows.  VCF input (pyseer/input.py:250-266, 383-407, 455-503) is read as text -- plain, gzip or BGZF -- by `VcfFile`
 (the `--python-reader` path and the yardstick) or by the native reader whose sample columns are tokenised on the device (`NativeVcfReader`,
-csrc/vcf_reader.cpp + csrc/vcf_kernels.hip).  No tabix index is read: burden regions are assigned in one pass over the file.
+csrc/vcf_reader.cpp + csrc/vcf_kernels.hip).  BCF 2.1 / 2.2, sniffed from the decoded bytes, takes the same two routes: `BcfFile`, and the
+native reader, which sends each record's GT vector to k_bcf_gt_pack.  No tabix index is read: burden regions are assigned in one pass over the file.
 """
 import binascii
 import gzip
 import hashlib
 import os
 import re
+import struct
 import sys
 
 import numpy as np
@@ -290,6 +292,263 @@ class VcfFile(object):
         return self._indexed[(contig, start, end)]
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# BCF 2.1 / 2.2 ("BCF input"): the binary form of the same records.  `BcfFile` is the `--python-reader` path and the yardstick of
+# the native BCF route (csrc/vcf_reader.cpp "BCF" + k_bcf_gt_pack); it parses with `struct` and shares nothing with the C++.
+# ---------------------------------------------------------------------------------------------------------------
+_BCF_WIDTH = {1: 1, 2: 2, 3: 4, 5: 4, 7: 1}
+_BCF_INT = {1: ('<i1', 0x80, 0x81), 2: ('<i2', 0x8000, 0x8001), 3: ('<i4', 0x80000000, 0x80000001)}   # dtype, missing, end of vector
+
+
+def _open_binary(path):
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    return gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")
+
+
+def is_bcf(path):
+    """True if the decoded bytes of `path` (plain, gzip or BGZF) start with the BCF magic: the name of the file does not count."""
+    try:
+        with _open_binary(path) as fh:
+            return fh.read(3) == b"BCF"
+    except (OSError, EOFError):
+        return False
+
+
+def _bcf_meta(line):
+    """(ID, IDX or None) of a `##KIND=<key=value,...>` header line; values may be quoted."""
+    body = line[line.index('<') + 1:]
+    out, i, n = {}, 0, len(body)
+    while i < n and body[i] != '>':
+        j = i
+        while j < n and body[j] not in '=,>':
+            j += 1
+        key, val = body[i:j], ''
+        if j < n and body[j] == '=':
+            j += 1
+            if j < n and body[j] == '"':
+                j += 1
+                while j < n and body[j] != '"':
+                    if body[j] == '\\' and j + 1 < n:
+                        j += 1
+                    val += body[j]
+                    j += 1
+                j += 1
+            else:
+                k = j
+                while j < n and body[j] not in ',>':
+                    j += 1
+                val = body[k:j]
+        out[key] = val
+        i = j + 1 if j < n and body[j] == ',' else j
+    idx = out.get('IDX')
+    return out.get('ID'), (int(idx) if idx is not None and idx.isdigit() and len(idx) < 10 else None)
+
+
+class _BcfCursor(object):
+    """Typed values out of one block of a record; every read is bounded by the block."""
+
+    def __init__(self, buf, what, number):
+        self.b, self.at, self.what, self.number = buf, 0, what, number
+
+    def fail(self, thing):
+        raise ValueError("BCF: record %d: %s runs past the %s block" % (self.number, thing, self.what))
+
+    def take(self, n, thing):
+        if n < 0 or self.at + n > len(self.b):
+            self.fail(thing)
+        self.at += n
+        return self.b[self.at - n:self.at]
+
+    def scalar(self, thing):
+        d = self.take(1, thing)[0]
+        if d >> 4 != 1 or d & 15 not in (1, 2, 3):
+            self.fail(thing)
+        w = _BCF_WIDTH[d & 15]
+        return int.from_bytes(self.take(w, thing), "little", signed=True)
+
+    def descriptor(self, thing):
+        d = self.take(1, thing)[0]
+        count = d >> 4
+        if count == 15:
+            count = self.scalar(thing)
+            if count < 0:
+                self.fail(thing)
+        return d & 15, count
+
+    def string(self, thing):
+        t, count = self.descriptor(thing)
+        if t == 0:
+            return ''
+        if t != 7:
+            self.fail(thing)
+        return self.take(count, thing).decode()
+
+
+class BcfRecord(object):
+    """One BCF record with VcfRecord's interface: contig, pos (1-based), ref, alt (the ALTs joined by commas), skip, name, codes()."""
+    __slots__ = ("contig", "pos", "ref", "alt", "skip", "name", "number", "n_sample", "n_fmt", "indiv", "gt_key")
+
+    def __init__(self, number, shared, indiv, contigs, gt_key, n_cols):
+        if len(shared) < 24:
+            raise ValueError("BCF: record %d: a shared block shorter than its fixed part" % number)
+        chrom, pos0, _rlen, _qual, ai, fs = struct.unpack_from("<iiifII", shared, 0)
+        n_allele, self.n_fmt, self.n_sample = ai >> 16, fs >> 24, fs & 0xffffff
+        if chrom not in contigs:
+            raise ValueError("BCF: record %d: CHROM index %d names no ##contig line of the header" % (number, chrom))
+        if self.n_sample not in (0, n_cols):
+            raise ValueError("BCF: record %d: n_sample is %d, the header has %d sample columns" % (number, self.n_sample, n_cols))
+        c = _BcfCursor(shared[24:], "shared", number)
+        c.string("ID")
+        alleles = [c.string("an allele") for _ in range(n_allele)]
+        t, count = c.descriptor("FILTER")
+        flt = []
+        if t != 0:
+            if t not in _BCF_INT:
+                c.fail("FILTER")
+            dt, mis, eov = _BCF_INT[t]
+            v = np.frombuffer(c.take(count * _BCF_WIDTH[t], "FILTER"), dtype=dt.replace('i', 'u'))
+            flt = [int(x) for x in v if x != mis and x != eov]
+        self.number, self.indiv, self.gt_key = number, indiv, gt_key
+        self.contig, self.pos = contigs[chrom], pos0 + 1
+        self.ref, self.alt = (alleles[0] if alleles else ''), ",".join(alleles[1:])
+        self.skip = VCF_MULTI if n_allele > 2 else (VCF_FILTERED if (flt and 0 not in flt) else VCF_KEPT)
+        self.name = "_".join([self.contig, str(self.pos), self.ref] + ([self.alt] if n_allele > 1 else []))
+
+    def name_all_alleles(self):
+        return self.name.replace(',', '_') if self.skip == VCF_MULTI else self.name
+
+    def _gt(self):
+        """The GT vector as an (n_sample, L) array of unsigned values with its missing and end-of-vector marks, or None."""
+        if self.n_sample == 0:
+            return None
+        c = _BcfCursor(self.indiv, "individual", self.number)
+        for _ in range(self.n_fmt):
+            key = c.scalar("a FORMAT field")
+            t, count = c.descriptor("a FORMAT field")
+            if t != 0 and t not in _BCF_WIDTH:
+                raise ValueError("BCF: record %d: a FORMAT field of unknown type %d" % (self.number, t))
+            data = c.take(count * _BCF_WIDTH.get(t, 0) * self.n_sample, "a FORMAT field")
+            if key == self.gt_key and self.gt_key is not None:
+                if t == 0 or count == 0:
+                    return None
+                if t not in _BCF_INT:
+                    raise ValueError("BCF: record %d: GT is not a vector of integers" % self.number)
+                dt, mis, eov = _BCF_INT[t]
+                return np.frombuffer(data, dtype=dt.replace('i', 'u')).reshape(self.n_sample, count).astype(np.int64), mis, eov
+        return None
+
+    def codes(self, n_cols, cache):
+        g = self._gt()
+        if g is None:
+            return [GT_MISSING] * n_cols
+        v, mis, eov = g
+        live = np.logical_and.accumulate(v != eov, axis=1)          # the values before the end-of-vector mark
+        allele = (v >> 1) - 1
+        present = (live & (v != mis) & (allele >= 1)).any(axis=1)
+        n_live = live.sum(axis=1)
+        last = v[np.arange(v.shape[0]), np.maximum(n_live - 1, 0)]
+        absent = ~present & (n_live > 0) & (last != mis) & ((last >> 1) == 1)
+        return np.where(present, GT_PRESENT, np.where(absent, GT_ABSENT, GT_MISSING)).tolist()
+
+
+class BcfFile(VcfFile):
+    """VcfFile's interface over a BCF 2.1 / 2.2 file (plain, gzip or BGZF bytes): samples, iteration, apply, prepare, fetch."""
+
+    def __init__(self, path):
+        self.path = path
+        self._cache = {}
+        self._indexed = {}
+        self._fh, self._contigs, self._gt_key, self.samples = self._open(path)
+        self._number = 0
+
+    @staticmethod
+    def _open(path):
+        fh = _open_binary(path)
+        head = fh.read(9)
+        if len(head) < 9 or head[:3] != b"BCF":
+            raise ValueError('%s: not a BCF file, or one that ends inside its head' % path)
+        if head[3] == 4:
+            raise ValueError('%s is BCF1 (BCF\\4), which is not read: BCF 2.1 and 2.2 are' % path)
+        if head[3] != 2:
+            raise ValueError('%s: BCF major version %d is not read: BCF 2.1 and 2.2 are' % (path, head[3]))
+        if head[4] not in (1, 2):
+            raise ValueError('%s: BCF minor version %d is not read: BCF 2.1 and 2.2 are' % (path, head[4]))
+        l_text = struct.unpack("<I", head[5:9])[0]
+        text = fh.read(l_text)
+        if len(text) < l_text:
+            raise ValueError('%s: BCF: the file ends inside its header text' % path)
+        text = text.split(b"\0", 1)[0].decode()
+        strings, contigs, samples, n_contig = {"PASS": 0}, {}, None, 0
+        for line in text.split("\n"):
+            line = line.rstrip("\r")
+            if line.startswith("##contig=<"):
+                name, idx = _bcf_meta(line)
+                if name is not None:
+                    contigs.setdefault(n_contig if idx is None else idx, name)
+                    n_contig += 1
+            elif line.startswith(("##FILTER=<", "##INFO=<", "##FORMAT=<")):
+                name, idx = _bcf_meta(line)
+                if name is not None and name not in strings:
+                    strings[name] = len(strings) if idx is None else idx
+            elif line.startswith("#CHROM"):
+                samples = [str(x) for x in line.split("\t")[9:]]
+        if samples is None:
+            raise ValueError('%s: the BCF header text has no #CHROM line' % path)
+        return fh, contigs, strings.get("GT"), samples
+
+    def _read(self, fh, number):
+        head = fh.read(8)
+        if not head:
+            return None
+        if len(head) < 8:
+            raise ValueError("BCF: the file ends inside the lengths of record %d" % number)
+        l_shared, l_indiv = struct.unpack("<II", head)
+        body = fh.read(l_shared + l_indiv)
+        if len(body) < l_shared + l_indiv:
+            raise ValueError("BCF: record %d: the file ends inside it" % number)
+        return BcfRecord(number, body[:l_shared], body[l_shared:], self._contigs, self._gt_key, len(self.samples))
+
+    def __next__(self):
+        self._number += 1
+        rec = self._read(self._fh, self._number)
+        if rec is None:
+            raise StopIteration
+        return rec
+
+    def prepare(self, intervals):
+        """One pass over the file for all the (contig, start, end) not looked up before: no index file is read."""
+        import bisect
+        todo = [iv for iv in dict.fromkeys(intervals) if iv not in self._indexed]
+        if not todo:
+            return
+        by_contig = {}
+        for iv in todo:
+            self._indexed[iv] = []
+            by_contig.setdefault(iv[0], []).append(iv)
+        starts, longest = {}, {}
+        for c, ivs in by_contig.items():
+            ivs.sort(key=lambda iv: iv[1])
+            starts[c] = [iv[1] for iv in ivs]
+            longest[c] = max(iv[2] - iv[1] for iv in ivs)
+        fh = self._open(self.path)[0]
+        with fh:
+            number = 0
+            while True:
+                number += 1
+                rec = self._read(fh, number)
+                if rec is None:
+                    break
+                if rec.contig not in by_contig:
+                    continue
+                a = rec.pos - 1
+                b = a + len(rec.ref)
+                ivs = by_contig[rec.contig]
+                for j in range(bisect.bisect_left(starts[rec.contig], a - longest[rec.contig]), bisect.bisect_left(starts[rec.contig], b)):
+                    if ivs[j][1] < b and a < ivs[j][2]:
+                        self._indexed[ivs[j]].append(rec)
+
+
 _REGION = re.compile(r'^(.+):(\d+)-(\d+)$')
 
 
@@ -302,7 +561,7 @@ def parse_region(region):
 def open_variant_file(var_type, var_file, burden_file=None, burden_regions=None, uncompressed=False):
     """(handle, sample_order) (input.py:268-299)."""
     if var_type == "vcf":
-        infile = VcfFile(var_file)
+        infile = BcfFile(var_file) if is_bcf(var_file) else VcfFile(var_file)
         if burden_file:
             load_burden(burden_file, burden_regions)
         return infile, []
@@ -612,7 +871,15 @@ class NativeVcfReader(object):
         C = self._C
         mode, ncols, ncontigs = C.c_int(0), C.c_int(0), C.c_int(0)
         self._abi.check(self._lib.sh_vcf_info(self._h, C.byref(mode), C.byref(ncols), C.byref(ncontigs)))
-        return {"container": ("plain", "gzip", "bgzf")[mode.value], "columns": ncols.value, "contigs": ncontigs.value}
+        d = {"container": ("plain", "gzip", "bgzf")[mode.value], "columns": ncols.value, "contigs": ncontigs.value}
+        if self.format != "vcf":                            # (a text file's dictionary stays what it was before BCF was read)
+            d["format"] = self.format
+        return d
+
+    @property
+    def format(self):
+        """'vcf' or 'bcf': what the decoded bytes hold (sh_vcf_format), whatever the file is called."""
+        return ("vcf", "bcf")[self._lib.sh_vcf_format(self._h)]
 
     def stats(self):
         C = self._C
