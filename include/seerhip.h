@@ -82,7 +82,8 @@ int         sh_warmup(int device);
  * waits).  Call before the first sh_warmup / sh_create.  Process-wide. */
 void        sh_set_wait_mode(int sleeping);
 
-/* one context per device; n_samples = len(p) of the reference */
+/* one context per device; n_samples = len(p) of the reference (at least 1: a context of a single sample serves the readers that tokenise on
+ * the device -- no model can be set up on it, as none can be fitted to one sample) */
 sh_ctx *sh_create(int device, int n_samples);
 void    sh_destroy(sh_ctx *ctx);
 /* enqueue all later work on this hipStream_t (NULL = the device's default stream) */
@@ -248,6 +249,18 @@ int64_t     sh_reader_buffered(sh_reader *r);
 /* gzip members decoded on several threads (csrc/inflate_par.h): chunks accepted so far that started from a SEARCHED block head (0: the
  * stream was decoded by one thread -- small file, stored/fixed blocks only, SEERHIP_ROUTE reader=serial, BGZF, plain text). */
 int64_t     sh_reader_par_chunks(sh_reader *r);
+/* The device route of the same reader: containers, inflate, CRC, line framing, names and the -2 accounting stay on the host as above; the
+ * sample tokens of every line are read on the device (k_kmer_pack, csrc/kmer_kernels.hip).  The decoder writes its text into pinned slabs,
+ * each slab goes to the device once on a stream of the reader's own (never the context's), a call sends one line table and brings the rows
+ * and counts back.  A reader opened this way answers sh_reader_next / _names_needed / _buffered / _par_chunks / _close / _error exactly as
+ * one from sh_reader_open does.  ctx: its N must be n_samples; NULL selects the kernel's rule restated in plain C++ (host_kmer_pack,
+ * csrc/kmer_kernels.h -- another code path than sh_reader_open's parser).  Refuses (NULL, sh_reader_error and sh_last_error) a sample
+ * count whose row does not fit the kernel's LDS.
+ * sh_reader_dev_stats: lines tokenised by the kernel / by the host restatement (a line longer than the pad that straddles two slabs, every
+ * line without a context), text bytes sent to the device, kernel launches.  sh_reader_dev_kernel_ms: the kernel's own time so far (events). */
+sh_reader  *sh_reader_open_dev(sh_ctx *ctx, const char *path, const char *const *sample_names, int n_samples);
+int         sh_reader_dev_stats(sh_reader *r, int64_t *lines_dev, int64_t *lines_host, int64_t *bytes_up, int64_t *launches);
+double      sh_reader_dev_kernel_ms(sh_reader *r);
 
 /* introspection: how many variants of the LAST batch went through the Firth kernel / its pinv slow path */
 int sh_glm_info(sh_ctx *ctx, int64_t *firth_routed, int64_t *pinv_routed);

@@ -10,6 +10,9 @@ tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 --lineage (MDS components or --lineage-clusters) runs fit_lineage_effect on the GPU as well (1 + lineages + covariates <= 50; --lineage-clusters
 without covariates: up to 1023 clusters).
 
+K-mer text goes through the native reader (csrc/reader.cpp), whose parser reads the sample tokens on the host; --device-reader (one file, one
+device) has them read on the device instead (k_kmer_pack), same bytes out; every other route ignores the flag.
+
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
 reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or
 line by line (--python-reader; also with --gpus, and for a header that names a sample twice).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
@@ -183,6 +186,9 @@ def get_options(argv=None):
                     help='Test every variant separately [Default: each distinct presence pattern of a block is tested once]')
     ot.add_argument('--python-reader', action='store_true', default=False,
                     help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
+    ot.add_argument('--device-reader', action='store_true', default=False,
+                    help='Read the sample tokens of one --kmers file on the device (the native reader; containers, lines and names stay on the host); '
+                         'ignored where another reader is used')
     ot.add_argument('--python-sink', action='store_true', default=False,
                     help='Format every output row in Python (one result tuple per variant) instead of the native block sink')
     ot.add_argument('--serial-sink', action='store_true', default=False,
@@ -522,9 +528,11 @@ def main(argv=None):
     elif native:
         if options.save_packed:
             cache_out = PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
+        # --device-reader (SEERHIP_ROUTE kmer_dev=1): the sample tokens are read on the first context's device, on a stream of the reader's own
+        dev_reader = (options.device_reader or _route.route("kmer_dev", "0") == "1") and options.gpus is None and bool(engs)
         blocks = iter_packed_blocks_native(p, var_file, options.min_af, options.max_af, job_block,
                                            want_patterns=want_pat, want_samples=options.print_samples,
-                                           save_to=cache_out, raw=job_path)
+                                           save_to=cache_out, raw=job_path, engine=(engs[0] if dev_reader else None))
     elif native_vcf:
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
         blocks = iter_packed_blocks_vcf_native(p, var_file, engs[0], options.min_af, options.max_af, options.max_missing, options.block_size,

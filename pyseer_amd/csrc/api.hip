@@ -24,6 +24,9 @@
 #include "vcf_reader.h"
 #include "rtab_kernels.h"
 #include "rtab_reader.h"
+#include "kmer_kernels.h"
+#include "reader_dev.h"
+#include <unordered_map>
 #include "enet_params.h"
 #include "patset_hash.h"
 extern "C" {
@@ -562,7 +565,7 @@ sh_ctx *sh_create(int device, int n_samples)
     if (const std::string bad = sh_route_unknown(); !bad.empty()) { g_err = "SEERHIP_ROUTE: unknown item '" + bad + "' (keys: csrc/route.h)"; return nullptr; }
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { g_err = "no HIP device: libseerhip has no CPU fallback"; return nullptr; }
     if (device < 0 || device >= n) { g_err = "bad device index"; return nullptr; }
-    if (n_samples < 2) { g_err = "n_samples must be >= 2"; return nullptr; }
+    if (n_samples < 1) { g_err = "n_samples must be >= 1"; return nullptr; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { g_err = "hipGetDeviceProperties failed"; return nullptr; }
     if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
@@ -1175,6 +1178,7 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "job_run.inc"
 #include "vcf_api.inc"
 #include "rtab_api.inc"
+#include "kmer_api.inc"
 #include "enet_api.inc"
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include <sys/stat.h>
 #include "../../include/seerhip.h"
 #include "inflate_fast.h"
+#include "reader_dev.h"
 
 // open-addressing table keyed by the sample name bytes (no per-token allocation; FNV-1a)
 struct NameTable {
@@ -145,11 +146,14 @@ struct sh_reader {
     std::deque<Slab> held; size_t cur = 0; const char *ptr = nullptr;     // slabs in hand, the one being read, next unread byte
     std::vector<char> bridge;            // a line longer than the pad that straddles two slabs (copied, rare)
     uint32_t crc_run = 0;
+    // device route (reader_dev.h): slab buffers come from the hooks, which also get the framed lines of a call instead of the parser below
+    bool hooked = false; ShReaderHooks hooks; size_t buf_bytes = 0;
     ~sh_reader() {
         { std::lock_guard<std::mutex> lk(mu); stop = true; }
         cv_put.notify_all(); cv_get.notify_all(); cv_free.notify_all();
         if (producer.joinable()) producer.join();
-        for (char *b : all_bufs) free(b);
+        for (char *b : all_bufs) { if (hooked) hooks.release(hooks.self, b); else free(b); }
+        if (hooked && hooks.destroy) hooks.destroy(hooks.self);
         if (map && map_len) munmap((void *)map, map_len);
         if (fd >= 0) close(fd);
         if (gz) gzclose(gz);
@@ -176,7 +180,7 @@ static char *get_buf(sh_reader *r)                                // nullptr whe
     // capped at 64: --block_size 65536 at N = 5000, ~2 GB of text per block, hung).  What bounds the memory is the block the caller asked
     // for plus the look-ahead of `depth` slabs (put_slab), not this function.
     if (r->free_bufs.empty()) {
-        char *b = (char *)malloc(r->pad_bytes + r->slab_bytes + 1024);
+        char *b = r->hooked ? r->hooks.alloc(r->hooks.self, r->buf_bytes) : (char *)malloc(r->pad_bytes + r->slab_bytes + 1024);
         if (b) { r->all_bufs.push_back(b); return b; }
     }
     r->cv_free.wait(lk, [&] { return r->stop || !r->free_bufs.empty(); });
@@ -188,6 +192,7 @@ static char *get_buf(sh_reader *r)                                // nullptr whe
 static void release_slab(sh_reader *r, Slab &sl)
 {
     if (!sl.mem) return;
+    if (r->hooked) r->hooks.slab_out(r->hooks.self, sl.mem);
     { std::lock_guard<std::mutex> lk(r->mu); r->free_bufs.push_back(sl.mem); }
     sl.mem = nullptr;
     r->cv_free.notify_one();
@@ -218,6 +223,26 @@ static void produce_plain(sh_reader *r)
         Slab sl;
         sl.len = std::min(r->slab_bytes, r->map_len - off);
         sl.data = (const char *)r->map + off; sl.pad = std::min(r->pad_bytes, off);
+        off += sl.len; sl.last = off >= r->map_len;
+        const bool last = sl.last;
+        if (!put_slab(r, std::move(sl)) || last) return;
+    }
+}
+
+// plain text of the device route: copied into slab buffers, each with the tail of the text before it as its pad (as the decoders leave them)
+static void produce_plain_copy(sh_reader *r)
+{
+    const size_t PAD = r->pad_bytes;
+    size_t off = 0;
+    for (;;) {
+        char *buf = get_buf(r);
+        if (!buf) return;
+        Slab sl; sl.mem = buf; sl.data = buf + PAD;
+        sl.len = std::min(r->slab_bytes, r->map_len - off); sl.pad = std::min(PAD, off);
+        // (one thread copies 10 GB/s, less than the route reads: the copy is shared out like the translation of the parallel decoder)
+        const uint8_t *src = r->map + off - sl.pad; char *dst = buf + PAD - sl.pad;
+        const size_t total = sl.pad + sl.len, PIECE = 1u << 20;
+        r->pool_bgzf->run((int64_t)((total + PIECE - 1) / PIECE), 1, [&](int64_t i) { memcpy(dst + (size_t)i * PIECE, src + (size_t)i * PIECE, std::min(PIECE, total - (size_t)i * PIECE)); });
         off += sl.len; sl.last = off >= r->map_len;
         const bool last = sl.last;
         if (!put_slab(r, std::move(sl)) || last) return;
@@ -533,11 +558,13 @@ const char *sh_reader_error(void) { return g_rerr.c_str(); }
 
 void sh_reader_set_concurrency(int n_readers) { shost::streams().store(n_readers < 1 ? 1 : n_readers); }      // (= sh_set_host_streams)
 
-sh_reader *sh_reader_open(const char *path, const char *const *sample_names, int n_samples)
+static sh_reader *reader_open(const char *path, const char *const *sample_names, int n_samples, const ShReaderHooks *hooks)
 {
+    struct Disown { const ShReaderHooks *h; ~Disown() { if (h && h->destroy) h->destroy(h->self); } } disown{hooks};      // (until the reader owns them)
     if (!path || !sample_names || n_samples < 1) { g_rerr = "bad argument"; return nullptr; }
     if (const std::string bad = sh_route_unknown(); !bad.empty()) { g_rerr = "SEERHIP_ROUTE: unknown item '" + bad + "' (keys: csrc/route.h)"; return nullptr; }
     sh_reader *r = new sh_reader();
+    if (hooks) { r->hooked = true; r->hooks = *hooks; disown.h = nullptr; }
     r->n = n_samples;
     r->index.build(sample_names, n_samples);
     int nt = reader_threads();
@@ -562,9 +589,14 @@ sh_reader *sh_reader_open(const char *path, const char *const *sample_names, int
     }
     if (const char *sb = sh_route("reader_slab")) r->slab_bytes = std::min<size_t>(2047u << 20, std::max<size_t>(70000, (size_t)std::atoll(sb)));   // (newline offsets are 32-bit)
     if (const char *pb = sh_route("reader_pad")) r->pad_bytes = std::max<size_t>(32768, (size_t)std::atoll(pb));
+    r->buf_bytes = r->pad_bytes + r->slab_bytes + 1024;
     if (r->map_len == 0) { r->eof = true; return r; }
     r->mode = (r->map_len >= 2 && r->map[0] == 0x1f && r->map[1] == 0x8b) ? (bgzf_member(r->map, r->map + r->map_len) ? 2 : 1) : 0;
     if (r->mode == 2) r->pool_bgzf.reset(new ParPool(std::max(1, std::min(32, std::max(2, nt / 2)) - 1), shost::ST_READER_DECODE));
+    // The device route: nobody parses, so the threads the parser would use decode (BGZF) or copy (plain text into the pinned slabs).  The
+    // parallel gzip decoder keeps its split: 12 decoding and 12 translating threads instead of 10 and 8 changed nothing (its acceptor's
+    // translation binds, profiles/r16/kmer_reader_dev.txt).  The host route's numbers stay as they are.
+    if (r->hooked && r->mode != 1) r->pool_bgzf.reset(new ParPool(std::max(1, std::min(32, nt) - 1), shost::ST_READER_DECODE));
     // one gzip member on several threads (inflate_par.h) unless SEERHIP_ROUTE reader=serial, or there is nothing to share out
     r->depth = std::max<size_t>(3, r->depth / (size_t)shost::host_streams());       // several readers at once share the memory as they share the CPUs
     if (const char *cd = sh_route("reader_depth")) r->depth = std::max<size_t>(1, (size_t)std::atoll(cd));
@@ -580,10 +612,12 @@ sh_reader *sh_reader_open(const char *path, const char *const *sample_names, int
         r->pool_bgzf.reset(new ParPool(helpers, shost::ST_READER_DECODE));
     }
     r->producer = std::thread([r, par] {
-        if (r->mode == 0) produce_plain(r); else if (r->mode == 1) { if (par) produce_gzip_parallel(r); else produce_gzip(r); } else produce_bgzf(r);
+        if (r->mode == 0) { if (r->hooked) produce_plain_copy(r); else produce_plain(r); } else if (r->mode == 1) { if (par) produce_gzip_parallel(r); else produce_gzip(r); } else produce_bgzf(r);
     });
     return r;
 }
+
+sh_reader *sh_reader_open(const char *path, const char *const *sample_names, int n_samples) { return reader_open(path, sample_names, n_samples, nullptr); }
 
 void sh_reader_close(sh_reader *r) { delete r; }
 
@@ -609,6 +643,10 @@ static bool next_slab(sh_reader *r, bool *failed)
         if (sl.err.empty()) r->crc_run = crc_parallel(r->pool.get(), r->crc_run, (const uint8_t *)sl.data + p, sl.len - p);
     }
     if (!sl.err.empty()) { g_rerr = sl.err; *failed = true; r->eof = true; release_slab(r, sl); return false; }
+    if (r->hooked && sl.mem) {
+        std::string err;
+        if (!r->hooks.slab_in(r->hooks.self, sl.mem, r->pad_bytes - sl.pad, r->pad_bytes + sl.len, err)) { g_rerr = err; *failed = true; r->eof = true; release_slab(r, sl); return false; }
+    }
     if (sl.last) r->eof = true;
     r->held.push_back(std::move(sl));
     return true;
@@ -741,6 +779,22 @@ int64_t sh_reader_next(sh_reader *r, int64_t max_variants, uint8_t *bits, int64_
     int64_t off = 0;
     for (int64_t v = 0; v < nv; ++v) { name_off[v] = off; memcpy(names + off, nm[v].first, nm[v].second - nm[v].first); off += nm[v].second - nm[v].first; }
     name_off[nv] = off;
+    if (r->hooked) {
+        // the device route: the lines as they lie in the slab buffers (in file order, like the slabs in hand) go to the hooks
+        std::vector<ShReaderLine> hl((size_t)nv);
+        size_t hi = 0;
+        for (int64_t v = 0; v < nv; ++v) {
+            const char *p = lines[v].first;
+            hl[v].p = p; hl[v].len = (size_t)(lines[v].second - p); hl[v].buf = nullptr;
+            if (r->gz || (!r->bridge.empty() && p == r->bridge.data())) continue;
+            auto holds = [&](const Slab &s) { return s.mem && p >= s.mem && p < s.mem + r->buf_bytes; };
+            while (hi < r->held.size() && !holds(r->held[hi])) ++hi;
+            if (hi < r->held.size()) hl[v].buf = r->held[hi].mem; else hi = 0;
+        }
+        std::string err;
+        if (!r->hooks.pack(r->hooks.self, hl.data(), nv, bits, row_bytes, counts, err)) { g_rerr = err; return -1; }
+        return nv;
+    }
     const auto &index = r->index;
     r->pool->run(nv, 8, [&](int64_t v) {
         const char *p = lines[v].first, *e = lines[v].second;
@@ -797,3 +851,7 @@ int64_t sh_reader_buffered(sh_reader *r)
 }
 
 }  // extern "C"
+
+sh_reader *sh_reader_open_hooked(const char *path, const char *const *sample_names, int n_samples, const ShReaderHooks &hooks) { return reader_open(path, sample_names, n_samples, &hooks); }
+void *sh_reader_hooks_self(sh_reader *r) { return r && r->hooked ? r->hooks.self : nullptr; }
+void sh_reader_set_error(const char *msg) { g_rerr = msg ? msg : ""; }

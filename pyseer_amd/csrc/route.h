@@ -44,6 +44,8 @@
 //                    many regions in a small file);  reader_workers=W  its decoding threads [2/3 of the reader's threads, at most 32]
 //   rtab_wg=64|256   [256] lanes per line of k_rtab_pack (one wavefront or a workgroup of four);  rtab_slab=B [32 MB] bytes per pinned slab of the
 //                    Rtab reader (small values: slabs that fill up and grow in a small file)
+//   kmer_dev=1       [0]  command line: one --kmers file read through the native reader has its sample tokens read on the device
+//                    (sh_reader_open_dev, k_kmer_pack), as --device-reader asks
 //   lin_counts=1|0   [unset] fit_lineage_effect on a design of cluster indicators without covariates by the count kernel (k_glm_lineage_counts,
 //                    glm_lineage.hip): unset, only where the dense kernels stop (1 + lineages > 50); 1, every such design; 0, never
 #pragma once
@@ -55,7 +57,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

@@ -780,9 +780,13 @@ def iter_packed_blocks(p, var_type, infile, all_strains, sample_order, min_af, m
 
 class NativeKmerReader(object):
     """Blocks of packed k-mer presence rows straight from the text file through libseerhip's reader (csrc/reader.cpp):
-    gzip inflate + tokenise + sample lookup + bit packing in C++ (OpenMP over the lines of a block).  No GPU needed."""
+    gzip inflate + tokenise + sample lookup + bit packing in C++ (OpenMP over the lines of a block).  No GPU needed.
+    engine: an Engine selects the device route (sh_reader_open_dev): the same containers, framing and names on the host, the sample tokens
+    read by k_kmer_pack on the engine's device, on a stream of the reader's own.  DEVICE_HOST_RULE instead of an engine selects the
+    library's host restatement of that kernel (checks without a device).  The blocks are the same arrays either way."""
+    DEVICE_HOST_RULE = "device-route-host-rule"
 
-    def __init__(self, path, sample_names, block_size=3000, max_name=256):
+    def __init__(self, path, sample_names, block_size=3000, max_name=256, engine=None):
         import ctypes as C
         from . import _abi
         self._C, self._abi = C, _abi
@@ -790,7 +794,12 @@ class NativeKmerReader(object):
         self.samples = [str(x) for x in sample_names]
         self.n = len(self.samples)
         arr = (C.c_char_p * self.n)(*[x.encode() for x in self.samples])
-        h = self._lib.sh_reader_open(str(path).encode(), arr, self.n)
+        self._engine = engine if engine is not None and engine != self.DEVICE_HOST_RULE else None      # (kept alive: the reader holds its context)
+        self.device_route = engine is not None
+        if engine is None:
+            h = self._lib.sh_reader_open(str(path).encode(), arr, self.n)
+        else:
+            h = self._lib.sh_reader_open_dev(self._engine._h if self._engine is not None else None, str(path).encode(), arr, self.n)
         if not h:
             raise IOError(self._lib.sh_reader_error().decode())
         self._h = C.c_void_p(h)
@@ -809,6 +818,15 @@ class NativeKmerReader(object):
             self.close()
         except Exception:
             pass
+
+    def dev_stats(self):
+        """The device route's counters (sh_reader_dev_stats): lines tokenised by the kernel / by the host restatement, text bytes sent to the
+        device, kernel launches, and the kernel's own time in ms."""
+        C = self._C
+        a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._abi.check(self._lib.sh_reader_dev_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"lines_dev": a.value, "lines_host": b.value, "bytes_up": c.value, "launches": d.value,
+                "kernel_ms": float(self._lib.sh_reader_dev_kernel_ms(self._h))}
 
     def raw_blocks(self):
         """(bits, counts, names_blob, name_off) per block; names stay one bytes blob + offsets (what the block sink consumes)."""
@@ -1379,13 +1397,15 @@ def _block_from_raw(n, samples, order, names, blob, off, bits, counts, min_af, m
     return blk
 
 
-def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, save_to=None, raw=False, say_empty=True):
+def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, save_to=None, raw=False, say_empty=True,
+                              engine=None):
     """Same PackedBlock stream as iter_packed_blocks for k-mer files, fed by the native reader.  save_to: a PackedCacheWriter that
-    receives every raw block (all parsed variants, before the AF filter).  raw: RawBlock objects for the job stream instead."""
+    receives every raw block (all parsed variants, before the AF filter).  raw: RawBlock objects for the job stream instead.
+    engine: the sample tokens are read on that engine's device (NativeKmerReader, --device-reader); the blocks are the same."""
     samples = [str(x) for x in p.index]
     order = sorted(range(len(samples)), key=lambda i: samples[i])
     n = len(samples)
-    reader = NativeKmerReader(path, samples, block_size)
+    reader = NativeKmerReader(path, samples, block_size, engine=engine)
     def finished():                      # the whole of a block's host preparation runs on the reader's thread, ahead of the engine
         for bits, counts, blob, off in reader.raw_blocks():
             if save_to is not None:

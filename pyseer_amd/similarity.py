@@ -7,6 +7,7 @@ import sys
 import numpy as np
 
 from . import __version__
+from . import _route
 
 block_size = 1000                      # pyseer/similarity.py:16 (sets the granularity of the 'Matrix size' progress lines)
 _FLUSH_ROWS = 1 << 16                  # packed rows handed to the device per call
@@ -30,6 +31,8 @@ def get_options(argv=None):
     parser.add_argument('--gpu', type=int, default=0, help='Device index [Default: 0]')
     parser.add_argument('--python-reader', action='store_true', default=False,
                         help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
+    parser.add_argument('--device-reader', action='store_true', default=False,
+                        help='Read the sample tokens of a --kmers file on the device (the native reader); ignored with --python-reader, --vcf and --pres')
     parser.add_argument('--version', action='version', version='%(prog)s ' + __version__)
     return parser.parse_args(argv)
 
@@ -79,12 +82,12 @@ class SimilarityAccumulator(object):
 
 
 def similarity_matrix(p, var_type, infile, path, all_strains, sample_order, min_af, max_af, max_missing, uncompressed,
-                      device=0, python_reader=False, progress=None):
+                      device=0, python_reader=False, progress=None, device_reader=False):
     """The loop of similarity.py:99-113 over PackedBlocks."""
     from .input import iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_rtab_native, iter_packed_blocks_vcf_native
     acc = SimilarityAccumulator(len(p), device=device)
     if var_type == "kmers" and not python_reader:
-        blocks = iter_packed_blocks_native(p, path, min_af, max_af, block_size)
+        blocks = iter_packed_blocks_native(p, path, min_af, max_af, block_size, engine=(acc.engine if device_reader else None))
     elif var_type == "vcf" and not python_reader:       # the sample columns are tokenised on the accumulator's device (pyseer/similarity.py:86-88)
         blocks = iter_packed_blocks_vcf_native(p, path, acc.engine, min_af, max_af, max_missing, block_size, want_patterns=False)
     elif var_type == "Rtab" and not python_reader:      # the calls likewise (k_rtab_pack)
@@ -139,6 +142,7 @@ def main(argv=None):
     K = similarity_matrix(p, var_type, infile, path, all_strains, sample_order, options.min_af, options.max_af,
                           options.max_missing, options.uncompressed, device=options.gpu,
                           python_reader=options.python_reader,
+                          device_reader=(options.device_reader or _route.route("kmer_dev", "0") == "1"),
                           progress=lambda n: sys.stderr.write('Matrix size ' + str(n) + '\n'))
     sys.stderr.write("Calculating sample similarity\n")
     pd.DataFrame(K, index=p.index, columns=p.index).to_csv(sys.stdout, sep='\t')

@@ -1,14 +1,20 @@
 """Throughput of the native k-mer reader (csrc/reader.cpp) on a synthetic k-mer file, N samples x V k-mers, by container:
 plain text, gzip through zlib's gzread (SEERHIP_ROUTE reader=zlib, the round-1 path), gzip through the in-tree inflate on one thread
 (SEERHIP_ROUTE reader=serial) and on several (the default, csrc/inflate_par.h), BGZF (member-parallel).
-No GPU involved; run it on the GPU host to see what feeds the engine there.  Prints one JSON line."""
+No GPU involved; run it on the GPU host to see what feeds the engine there.  Prints one JSON line.
+
+--device: the same generated file (N = 5000; 40 000 k-mers unless V says otherwise) through the host route (sh_reader_open) and the device route
+(sh_reader_open_dev, k_kmer_pack) alternately in ONE process, for plain text, gzip and BGZF: a warm-up pass of each, then 3 passes of each; the
+medians, the spread of the host passes (the yardstick, timed in the same run), the device route's counters and the kernel's own time (events).
+Every pass of either route is checked against the first pass's carrier count."""
 import gzip, json, os, struct, sys, time, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pyseer_amd.input import NativeKmerReader
 
-N = int(os.environ.get("N", 5000)); V = int(os.environ.get("V", 12000)); BS = int(os.environ.get("BLOCK", 4096))
+DEVICE = "--device" in sys.argv[1:]
+N = int(os.environ.get("N", 5000)); V = int(os.environ.get("V", 40000 if DEVICE else 12000)); BS = int(os.environ.get("BLOCK", 4096))
 d = os.environ.get("OUT", "/tmp/rb"); os.makedirs(d, exist_ok=True)
 rng = np.random.default_rng(0)
 names = ["sample_%05d" % i for i in range(N)]
@@ -38,6 +44,40 @@ else:
     json.dump([N, V], open(d + "/meta.json", "w"))
 gen = time.time() - t0
 res = {"n_samples": N, "kmers": V, "text_MB": len(text) / 1e6, "gz_MB": os.path.getsize(d + "/k.gz") / 1e6, "cores": os.cpu_count(), "generate_s": gen}
+if DEVICE:
+    from pyseer_amd.engine import Engine
+    eng = Engine(N)
+    PASSES = int(os.environ.get("REPS", 3))
+
+    def one_pass(path, engine):
+        t0 = time.time(); tot = 0; cs = 0
+        r = NativeKmerReader(path, names, BS, engine=engine)
+        for bits, counts, blob, off in r.raw_blocks():
+            tot += counts.shape[0]; cs += int(counts.sum())
+        st = r.dev_stats() if engine is not None else None
+        r.close()
+        assert tot == V
+        return time.time() - t0, cs, st
+    for tag, path in (("plain", "k.txt"), ("gzip", "k.gz"), ("bgzf", "k.bgzf.gz")):
+        path = d + "/" + path
+        _, want_cs, _ = one_pass(path, None)                   # warm-up passes (page cache, pinned memory, the module's kernels)
+        _, cs, _ = one_pass(path, eng)
+        assert cs == want_cs, (tag, cs, want_cs)
+        th, td, st = [], [], None
+        for rep in range(PASSES):
+            t, cs, _ = one_pass(path, None); assert cs == want_cs; th.append(t)
+            t, cs, st = one_pass(path, eng); assert cs == want_cs; td.append(t)
+        mh, md = float(np.median(th)), float(np.median(td))
+        res[tag] = {"host_kmers_per_s": V / mh, "host_min_max_kmers_per_s": [V / max(th), V / min(th)], "device_kmers_per_s": V / md,
+                    "device_min_max_kmers_per_s": [V / max(td), V / min(td)], "device_over_host": mh / md, "dev_stats": st,
+                    "kernel_share_of_pass": st["kernel_ms"] * 1e-3 / td[-1]}
+        sys.stderr.write("%-5s host %7.0f k-mers/s (passes %.0f .. %.0f)   device %7.0f k-mers/s (passes %.0f .. %.0f)   x%.2f   kernel %.1f ms of the last %.0f ms pass, "
+                         "%d launches, %.0f MB up, lines on the device %d / on the host %d\n"
+                         % (tag, V / mh, V / max(th), V / min(th), V / md, V / max(td), V / min(td), mh / md, st["kernel_ms"], td[-1] * 1e3, st["launches"],
+                            st["bytes_up"] / 1e6, st["lines_dev"], st["lines_host"]))
+    eng.close()
+    res["block"] = BS; res["passes"] = PASSES
+    print(json.dumps(res)); sys.exit(0)
 want = None
 TAGS = os.environ.get("TAGS", "").split(",") if os.environ.get("TAGS") else None
 for tag, path, env in (("plain", "k.txt", None), ("gzip_zlib", "k.gz", "zlib"), ("gzip_fast", "k.gz", "serial"), ("gzip_par", "k.gz", None), ("bgzf", "k.bgzf.gz", None)):
