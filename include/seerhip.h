@@ -542,6 +542,28 @@ int64_t     sh_nameset_match(sh_nameset *set, const char *blob, const int64_t *o
 int64_t     sh_nameset_left(const sh_nameset *set);
 void        sh_nameset_free(sh_nameset *set);
 
+/* ---------------------------------------------------------------------------------------------
+ * A packed cache served to a subset or another order of its samples (csrc/select_kernels.hip k_rows_select + csrc/select_api.inc;
+ * pyseer_amd/input.py iter_packed_blocks_cached with `select`).  A cache written over samples S holds every parsed line of the k-mer file;
+ * a run over n_dst of them, in any order, sees the same lines with bit j of a row = bit map[j] of the stored row.
+ *   open: map[n_dst] (host) names distinct source bits, each in [0, n_src); n_dst must be the context's n_samples.  The table is uploaded;
+ *     the selector owns a stream and pinned staging of its own and runs beside the context's job stream and lanes.  NULL on error
+ *     (sh_last_error); n_src above what a source row may take of the LDS (64 KB: 524 288 samples) is refused.
+ *   rows: V host rows of src_row_bytes (a multiple of 8, at least n_src bits) -> V host rows of ((n_dst + 63) / 64) * 8 bytes, every bit at or
+ *     above n_dst zero whatever the source's padding bits hold, and each row's carrier count among the n_dst samples.  Complete when the call
+ *     returns.  src_is_dma != 0: `bits` lies in memory the device may read where it is (sh_host_register); out_bits may be any host memory.
+ *   rows_dev: the same with rows, output and counts in device memory (8-byte aligned), on the selector's stream; complete at return.
+ *   rows_host: the rule restated in plain C++ on the host pool, no context and no device: checks, and the rate to compare against.
+ * One thread per selector at a time.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sh_select sh_select;
+sh_select  *sh_select_open(sh_ctx *ctx, int n_src, const int32_t *map, int n_dst);
+void        sh_select_close(sh_select *s);
+int         sh_select_rows(sh_select *s, const uint8_t *bits, int64_t src_row_bytes, int64_t V, uint8_t *out_bits, int32_t *out_counts, int src_is_dma);
+int         sh_select_rows_dev(sh_select *s, const void *d_bits, int64_t src_row_bytes, int64_t V, void *d_out, int32_t *d_counts);
+int         sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits,
+                                int32_t *out_counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,7 +94,7 @@ import pandas as pd
 
 from . import __version__
 from .classes import Seer, LMM, FLAG_FILTER, FLAG_PREFILTER, notes_from_flags
-from .input import (check_kmers_gzipped, check_packed_cache, plan_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
+from .input import (announce_cache_select, check_kmers_gzipped, check_packed_cache, plan_packed_cache, load_phenotypes, load_structure, load_covariates, load_lineage, open_variant_file,
                     iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_native_multi, iter_packed_blocks_cached,
                     iter_packed_blocks_vcf_native, iter_packed_blocks_rtab_native, load_burden,
                     PackedCacheWriter, packed_cache_complete)
@@ -174,12 +174,13 @@ def get_options(argv=None):
                     'From a packed cache every GPU tests its own contiguous range of the rows through its own pipeline; other input is one stream '
                     'whose blocks go to the GPUs in turn. Output keeps the input order [Default: the single --gpu]')
     ot.add_argument('--save-packed', default=None,
-                    help='Also write the parsed k-mer file as packed bit rows (for --load-packed in later runs over the same samples)')
+                    help='Also write the parsed k-mer file as packed bit rows (for --load-packed in later runs over the same samples, or any subset or order of them)')
     ot.add_argument('--packed-cache', action='store_true', default=False,
                     help='Keep a packed cache next to the k-mer file (<kmers>.seerpack): written by the first run, read by later runs '
                          'over the same samples while the k-mer file is unchanged (size and modification time); ignored with a warning otherwise')
     ot.add_argument('--load-packed', default=None,
-                    help='Read variants from a packed cache written by --save-packed instead of parsing --kmers again')
+                    help='Read variants from a packed cache written by --save-packed or python -m pyseer_amd.pack instead of parsing --kmers again; the cache may '
+                         'hold more samples than the run, in any order (its rows are then selected on one device)')
     ot.add_argument('--cpu-eigh', action='store_true', default=False,
                     help='Decompose the similarity matrix with numpy on the host instead of rocSOLVER on the GPU')
     ot.add_argument('--no-dedup', action='store_true', default=False,
@@ -444,6 +445,18 @@ def main(argv=None):
     if not options.lineage:
         lineage_dict = None
 
+    # --load-packed of a cache over a superset or another order of the run's samples (input.py iter_packed_blocks_cached, select): its rows
+    # are restricted and permuted on the first device while the cache is read, in the Python block loop of one device.  (A cache that cannot
+    # be used at all raises where it always has: at the library's header check or at the first block, behind the header line.)
+    cache_selected = False
+    if options.load_packed:
+        try:
+            cache_selected = announce_cache_select(p, options.load_packed, select="device")
+        except (ValueError, IOError, OSError):
+            pass
+        if cache_selected and ((devs_ is not None and len(devs_) > 1) or options.packed_part):
+            _die("pyseer_amd: a packed cache over other samples than the run's own list is read on one device: not with --gpus or --packed-part\n")
+
     all_strains = set(p.index)
     kmer_files = list(options.kmers) if options.kmers else []
     if options.load_packed and options.save_packed and os.path.realpath(options.load_packed) == os.path.realpath(options.save_packed):
@@ -521,7 +534,8 @@ def main(argv=None):
     if options.load_packed:
         blocks = iter_packed_blocks_cached(p, options.load_packed, options.min_af, options.max_af, job_block,
                                            want_patterns=want_pat, want_samples=options.print_samples,
-                                           raw=job_path, device=(engs[0].device if (job_path and engs) else None), ahead=job_ahead)
+                                           raw=job_path, device=(engs[0].device if (job_path and engs) else None), ahead=job_ahead,
+                                           select=(engs[0] if cache_selected else None))
     elif native and len(kmer_files) > 1:
         blocks = iter_packed_blocks_native_multi(p, kmer_files, options.min_af, options.max_af, job_block,
                                                  want_patterns=want_pat, want_samples=options.print_samples, raw=job_path)
@@ -971,7 +985,8 @@ def main(argv=None):
     thread_cpu = {}                                        # CPU seconds of the Python threads of the block loop, by role (time.thread_time)
     # a packed cache through the job stream: the block loop runs inside the library, one call per device (SEERHIP_ROUTE job=py: the loop in
     # Python, as round 5 had it and as text input still has it)
-    packed_c_loop = bool(job_path and options.load_packed and _route.route("job", "1") != "py" and has_fd(sys.stdout)
+    # (the library's loop takes a cache of the run's own samples only: a selected cache goes through the Python loop)
+    packed_c_loop = bool(job_path and options.load_packed and not cache_selected and _route.route("job", "1") != "py" and has_fd(sys.stdout)
                          and (patterns is None or has_fd(patterns)))
     if packed_c_loop:
         check_packed_cache(p, options.load_packed)

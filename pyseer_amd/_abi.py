@@ -148,6 +148,12 @@ SIGNATURES = {
     "sh_nameset_match": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sh_nameset_left": (C.c_int64, [C.c_void_p]),
     "sh_nameset_free": (None, [C.c_void_p]),
+    # a packed cache served to a subset / another order of its samples (csrc/select_kernels.hip, csrc/select_api.inc)
+    "sh_select_open": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "sh_select_close": (None, [C.c_void_p]),
+    "sh_select_rows": (C.c_int, [C.c_void_p, c_u8p, C.c_int64, C.c_int64, c_u8p, C.POINTER(C.c_int32), C.c_int]),
+    "sh_select_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sh_select_rows_host": (C.c_int, [c_u8p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, c_u8p, C.POINTER(C.c_int32)]),
 }
 
 

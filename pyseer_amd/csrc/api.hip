@@ -1180,5 +1180,6 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "rtab_api.inc"
 #include "kmer_api.inc"
 #include "enet_api.inc"
+#include "select_api.inc"
 
 }  // extern "C"

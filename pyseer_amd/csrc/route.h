@@ -48,6 +48,9 @@
 //                    (sh_reader_open_dev, k_kmer_pack), as --device-reader asks
 //   lin_counts=1|0   [unset] fit_lineage_effect on a design of cluster indicators without covariates by the count kernel (k_glm_lineage_counts,
 //                    glm_lineage.hip): unset, only where the dense kernels stop (1 + lineages > 50); 1, every such design; 0, never
+//   cache_select=0|host [unset] a packed cache whose samples are a superset or another order of the run's (input.py iter_packed_blocks_cached):
+//                    unset, its rows are restricted and permuted on the device (k_rows_select); host, by the host restatement
+//                    (sh_select_rows_host); 0, such a cache is refused as a cache of other samples always was
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -57,7 +60,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

@@ -1,0 +1,197 @@
+// select_api.inc -- sh_select_* (include/seerhip.h): the rows of a packed cache restricted to, and permuted into, the samples of a run
+// (included by api.hip inside its extern "C" block; the kernel: select_kernels.hip).
+//
+// A selector belongs to a context (its device, its N = n_dst) but owns a stream and its staging, like the device k-mer reader
+// (kmer_api.inc): it runs on the reader's thread beside the context's job stream and lanes and never waits for them.
+//   sh_select_rows        host rows in chunks of about 16 MB through two slots: chunk c is copied into pinned memory (the host pool; not for
+//                         rows that lie in registered memory), goes up, through k_rows_select and back into pinned memory while chunk c - 1
+//                         is copied out to the caller -- three PCIe crossings per row in all, counting the engine's own upload afterwards;
+//   sh_select_rows_dev    rows that are on the device already: one launch on the selector's stream, complete when the call returns;
+//   sh_select_rows_host   the same rule in plain C++ on the host pool, no context: the CPU tests, and the rate to compare against.
+hipError_t shk_rows_select(hipStream_t, const void *, int64_t, int64_t, const int32_t *, int, void *, int32_t *);
+int64_t shk_rows_select_max_row_bytes(void);
+
+#define SELECT_CHUNK_BYTES ((int64_t)16 << 20)
+
+struct sh_select {
+    sh_ctx *ctx = nullptr; int device = 0, n_src = 0, n_dst = 0;
+    hipStream_t stream = nullptr;
+    int32_t *d_map = nullptr;
+    struct Slot { uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr; int32_t *h_counts = nullptr, *d_counts = nullptr;
+                  int64_t cap_in = 0, cap_rows = 0; hipEvent_t done = nullptr; } slot[2];
+};
+
+// every entry in [0, n_src), no entry twice
+static int select_check_map(int n_src, const int32_t *map, int n_dst, const char *who)
+{
+    if (n_src < 1 || n_dst < 1 || !map) return fail(SH_EINVAL, std::string(who) + ": bad argument");
+    if (n_dst > n_src) return fail(SH_ESHAPE, std::string(who) + ": more samples selected than the rows hold");
+    std::vector<uint8_t> seen((size_t)n_src, 0);
+    for (int j = 0; j < n_dst; ++j) {
+        if (map[j] < 0 || map[j] >= n_src) return fail(SH_EINVAL, std::string(who) + ": map entry " + std::to_string(j) + " is outside the source row (" + std::to_string(map[j]) + ")");
+        if (seen[(size_t)map[j]]) return fail(SH_EINVAL, std::string(who) + ": source sample " + std::to_string(map[j]) + " is selected twice");
+        seen[(size_t)map[j]] = 1;
+    }
+    return SH_OK;
+}
+
+static int select_check_rows(int n_src, int64_t src_row_bytes, int64_t V, const void *in, const void *out, const void *counts, const char *who)
+{
+    if (V < 0 || src_row_bytes <= 0 || (V > 0 && (!in || !out || !counts))) return fail(SH_EINVAL, std::string(who) + ": bad argument");
+    if (src_row_bytes & 7) return fail(SH_ESHAPE, std::string(who) + ": src_row_bytes must be a multiple of 8");
+    if (src_row_bytes * 8 < n_src) return fail(SH_ESHAPE, std::string(who) + ": src_row_bytes*8 < n_src");
+    return SH_OK;
+}
+
+void sh_select_close(sh_select *s)
+{
+    if (!s) return;
+    hipSetDevice(s->device);
+    if (s->stream) hipStreamSynchronize(s->stream);
+    for (auto &sl : s->slot) {
+        if (sl.h_in) hipHostFree(sl.h_in);
+        if (sl.h_out) hipHostFree(sl.h_out);
+        if (sl.h_counts) hipHostFree(sl.h_counts);
+        hipFree(sl.d_in); hipFree(sl.d_out); hipFree(sl.d_counts);
+        if (sl.done) hipEventDestroy(sl.done);
+    }
+    hipFree(s->d_map);
+    if (s->stream) hipStreamDestroy(s->stream);
+    delete s;
+}
+
+static int select_open_device(sh_select *s, const int32_t *map)
+{
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    for (auto &sl : s->slot) HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    HIPCHK(dmalloc(&s->d_map, (size_t)s->n_dst));
+    HIPCHK(hipMemcpyAsync(s->d_map, map, (size_t)s->n_dst * 4, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));                // (the caller's table is pageable and its own again from here on)
+    return SH_OK;
+}
+
+sh_select *sh_select_open(sh_ctx *ctx, int n_src, const int32_t *map, int n_dst)
+{
+    if (!ctx) { fail(SH_EINVAL, "sh_select_open: null ctx"); return nullptr; }
+    if (ctx->N != n_dst) { fail(SH_ESHAPE, "sh_select_open: the context was created for another number of samples than the map selects"); return nullptr; }
+    if (select_check_map(n_src, map, n_dst, "sh_select_open") != SH_OK) return nullptr;
+    if ((((int64_t)n_src + 63) / 64) * 8 > shk_rows_select_max_row_bytes()) {
+        fail(SH_ESHAPE, "sh_select_open: too many source samples for k_rows_select's row in LDS (at most " + std::to_string(shk_rows_select_max_row_bytes() * 8) + ")");
+        return nullptr;
+    }
+    sh_select *s = new sh_select();
+    s->ctx = ctx; s->device = ctx->device; s->n_src = n_src; s->n_dst = n_dst;
+    if (select_open_device(s, map) != SH_OK) { const std::string keep = g_err; sh_select_close(s); fail(SH_EHIP, keep); return nullptr; }
+    return s;
+}
+
+static int select_ensure(sh_select *s, sh_select::Slot &sl, int64_t rows, int64_t in_bytes, bool stage_in)
+{
+    const int64_t out_rb = (((int64_t)s->n_dst + 63) / 64) * 8;
+    if (in_bytes > sl.cap_in) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (sl.h_in) hipHostFree(sl.h_in);
+        hipFree(sl.d_in); sl.h_in = sl.d_in = nullptr; sl.cap_in = 0;
+        HIPCHK(hipMalloc((void **)&sl.d_in, (size_t)in_bytes));
+        sl.cap_in = in_bytes;
+    }
+    if (stage_in && !sl.h_in) HIPCHK(hipHostMalloc((void **)&sl.h_in, (size_t)sl.cap_in, hipHostMallocDefault));
+    if (rows > sl.cap_rows) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (sl.h_out) hipHostFree(sl.h_out);
+        if (sl.h_counts) hipHostFree(sl.h_counts);
+        hipFree(sl.d_out); hipFree(sl.d_counts);
+        sl.h_out = sl.d_out = nullptr; sl.h_counts = sl.d_counts = nullptr; sl.cap_rows = 0;
+        HIPCHK(hipHostMalloc((void **)&sl.h_out, (size_t)(rows * out_rb), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&sl.h_counts, (size_t)rows * 4, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&sl.d_out, (size_t)(rows * out_rb)));
+        HIPCHK(dmalloc(&sl.d_counts, (size_t)rows));
+        sl.cap_rows = rows;
+    }
+    return SH_OK;
+}
+
+// nbytes from src to dst on the host pool, in pieces of 1 MB
+static void select_copy(uint8_t *dst, const uint8_t *src, int64_t nbytes)
+{
+    const int64_t piece = (int64_t)1 << 20, n = (nbytes + piece - 1) / piece;
+    const std::function<void(int64_t)> fn = [&](int64_t i) { memcpy(dst + i * piece, src + i * piece, (size_t)std::min(piece, nbytes - i * piece)); };
+    shost::CpuScope cs(shost::ST_STAGE_COPY);
+    shost::pool().run(n, 1, fn, shost::ST_STAGE_COPY, shost::per_stream_cpus());
+}
+
+int sh_select_rows(sh_select *s, const uint8_t *bits, int64_t src_row_bytes, int64_t V, uint8_t *out_bits, int32_t *out_counts, int src_is_dma)
+{
+    if (!s) return fail(SH_EINVAL, "sh_select_rows: null selector");
+    const int rc0 = select_check_rows(s->n_src, src_row_bytes, V, bits, out_bits, out_counts, "sh_select_rows"); if (rc0) return rc0;
+    if (src_row_bytes > shk_rows_select_max_row_bytes()) return fail(SH_ESHAPE, "sh_select_rows: the source row is too wide for k_rows_select's row in LDS");
+    if (V == 0) return SH_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const int64_t out_rb = (((int64_t)s->n_dst + 63) / 64) * 8;
+    const int64_t chunk = std::max<int64_t>(1, SELECT_CHUNK_BYTES / src_row_bytes), n_chunks = (V + chunk - 1) / chunk;
+    // chunk c's results are complete (its slot's event) and go to the caller
+    auto finish = [&](int64_t c) -> int {
+        sh_select::Slot &sl = s->slot[c & 1];
+        const int64_t v0 = c * chunk, nv = std::min(chunk, V - v0);
+        HIPCHK(hipEventSynchronize(sl.done));
+        select_copy(out_bits + v0 * out_rb, sl.h_out, nv * out_rb);
+        memcpy(out_counts + v0, sl.h_counts, (size_t)nv * 4);
+        return SH_OK;
+    };
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        sh_select::Slot &sl = s->slot[c & 1];
+        if (c >= 2) { const int rc = finish(c - 2); if (rc) return rc; }
+        const int64_t v0 = c * chunk, nv = std::min(chunk, V - v0);
+        const int rc = select_ensure(s, sl, std::min(chunk, V), std::min(chunk, V) * src_row_bytes, !src_is_dma); if (rc) return rc;
+        const uint8_t *from = bits + v0 * src_row_bytes;
+        if (!src_is_dma) { select_copy(sl.h_in, from, nv * src_row_bytes); from = sl.h_in; }
+        HIPCHK(hipMemcpyAsync(sl.d_in, from, (size_t)(nv * src_row_bytes), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(shk_rows_select(s->stream, sl.d_in, src_row_bytes, nv, s->d_map, s->n_dst, sl.d_out, sl.d_counts));
+        HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)(nv * out_rb), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_counts, sl.d_counts, (size_t)nv * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipEventRecord(sl.done, s->stream));
+    }
+    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c) { const int rc = finish(c); if (rc) return rc; }
+    return SH_OK;
+}
+
+int sh_select_rows_dev(sh_select *s, const void *d_bits, int64_t src_row_bytes, int64_t V, void *d_out, int32_t *d_counts)
+{
+    if (!s) return fail(SH_EINVAL, "sh_select_rows_dev: null selector");
+    const int rc0 = select_check_rows(s->n_src, src_row_bytes, V, d_bits, d_out, d_counts, "sh_select_rows_dev"); if (rc0) return rc0;
+    if (src_row_bytes > shk_rows_select_max_row_bytes()) return fail(SH_ESHAPE, "sh_select_rows_dev: the source row is too wide for k_rows_select's row in LDS");
+    if ((((uintptr_t)d_bits) | ((uintptr_t)d_out)) & 7) return fail(SH_EINVAL, "sh_select_rows_dev: rows must be 8-byte aligned");
+    if (V == 0) return SH_OK;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(shk_rows_select(s->stream, d_bits, src_row_bytes, V, s->d_map, s->n_dst, d_out, d_counts));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return SH_OK;
+}
+
+// the kernel's rule in plain C++: out bit j = source bit map[j]; whole output rows are written, pad bits zero
+int sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits, int32_t *out_counts)
+{
+    const int rc0 = select_check_map(n_src, map, n_dst, "sh_select_rows_host"); if (rc0) return rc0;
+    if (V < 0 || src_row_bytes <= 0 || (V > 0 && (!bits || !out_bits || !out_counts))) return fail(SH_EINVAL, "sh_select_rows_host: bad argument");
+    if (src_row_bytes * 8 < n_src) return fail(SH_ESHAPE, "sh_select_rows_host: src_row_bytes*8 < n_src");
+    const int64_t out_rb = (((int64_t)n_dst + 63) / 64) * 8;
+    const int out_words = (n_dst + 63) >> 6;
+    const std::function<void(int64_t)> fn = [&](int64_t v) {
+        const uint8_t *row = bits + v * src_row_bytes;
+        uint8_t *o = out_bits + v * out_rb;
+        int cnt = 0;
+        for (int w = 0; w < out_words; ++w) {
+            uint64_t word = 0;
+            const int n = std::min(64, n_dst - 64 * w);
+            const int32_t *m = map + 64 * w;
+            for (int l = 0; l < n; ++l) word |= (uint64_t)((row[m[l] >> 3] >> (m[l] & 7)) & 1u) << l;
+            cnt += __builtin_popcountll(word);
+            memcpy(o + 8 * w, &word, 8);
+        }
+        out_counts[v] = cnt;
+    };
+    shost::CpuScope cs(shost::ST_OTHER);
+    shost::pool().run(V, 64, fn, shost::ST_OTHER);
+    return SH_OK;
+}

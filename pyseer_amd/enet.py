@@ -505,11 +505,11 @@ def run_cli(options, p, cov, m, null_fit, firth_null, lineage_clusters, lineage_
         infile, sample_order = open_variant_file(var_type, var_file, options.burden, regions, options.uncompressed)
         return infile, sample_order, regions
     names = counts = kept = None
+    engine = Engine(len(p), device=options.gpu)
     if native:
         from .input import open_kmer_block_stream
-        blocks, cache_out = open_kmer_block_stream(options, p, kmers, max(options.block_size, 1 << 18))
+        blocks, cache_out = open_kmer_block_stream(options, p, kmers, max(options.block_size, 1 << 18), select=engine)
     err.write("Reading all variants\n")
-    engine = Engine(len(p), device=options.gpu)
     if native:
         try:
             M, var_indices, loaded, blob, off, counts = load_all_vars_blocks(engine, p, blocks, options.min_af, options.max_af, options.max_missing)

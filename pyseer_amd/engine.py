@@ -442,4 +442,76 @@ def hash_rows(bits, n_samples):
     return keys
 
 
-__all__ = ["Engine", "Job", "PatternSet", "hash_rows", "pack_variants", "row_bytes_for"]
+def _select_map(n_src, sample_map):
+    m = np.ascontiguousarray(sample_map, dtype=np.int32).reshape(-1)
+    return int(n_src), m, m.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _select_rows_in(bits, n_src):
+    bits = np.require(bits, dtype=np.uint8, requirements=["C"])
+    if bits.ndim != 2 or bits.shape[1] * 8 < n_src:
+        raise AssertionError("rows of %s bytes do not hold %d samples" % (bits.shape[1:] or "?", n_src))
+    return bits
+
+
+class RowSelector(object):
+    """Packed rows over n_src samples -> rows over the engine's samples, bit j = source bit sample_map[j] (include/seerhip.h sh_select_*,
+    k_rows_select): what serves a packed cache to a subset or another order of its samples.  sample_map: len == engine.n, distinct, each
+    in [0, n_src).  Works on a stream of its own; one thread at a time."""
+
+    def __init__(self, engine, n_src, sample_map):
+        self._lib = engine._lib
+        self._eng = engine
+        self.n_src, self.map, mp = _select_map(n_src, sample_map)
+        self.n_dst = int(self.map.shape[0])
+        self.row_bytes = row_bytes_for(self.n_dst)
+        h = self._lib.sh_select_open(engine._h, self.n_src, mp, self.n_dst)
+        if not h:
+            raise _abi.SeerHipError(_abi.SH_EINVAL, self._lib.sh_last_error().decode())
+        self._h = C.c_void_p(h)
+
+    def select(self, bits, dma=False):
+        """bits (V, src_row_bytes) uint8 host rows -> (rows (V, row_bytes_for(n_dst)) uint8, counts (V,) int32), complete at return.
+        dma: the rows lie in memory registered for the device (sh_host_register)."""
+        bits = _select_rows_in(bits, self.n_src)
+        V = bits.shape[0]
+        out = np.empty((V, self.row_bytes), dtype=np.uint8); counts = np.empty(V, dtype=np.int32)
+        if V:
+            _abi.check(self._lib.sh_select_rows(self._h, bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], V, out.ctypes.data_as(_abi.c_u8p),
+                                                counts.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(dma))))
+        return out, counts
+
+    def select_dev(self, bits_t):
+        """The same for a (V, src_row_bytes) uint8 tensor on the engine's device -> (rows, counts) tensors there."""
+        import torch
+        V, rb = bits_t.shape
+        out = torch.empty((V, self.row_bytes), dtype=torch.uint8, device=bits_t.device)
+        counts = torch.empty((V,), dtype=torch.int32, device=bits_t.device)
+        torch.cuda.current_stream(bits_t.device).synchronize()       # (the selector's stream is its own: the rows must be there)
+        _abi.check(self._lib.sh_select_rows_dev(self._h, C.c_void_p(bits_t.data_ptr()), rb, V, C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr())))
+        return out, counts
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sh_select_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def select_rows_host(bits, n_src, sample_map):
+    """RowSelector.select by the host restatement (sh_select_rows_host; no device): -> (rows, counts)."""
+    n_src, m, mp = _select_map(n_src, sample_map)
+    bits = _select_rows_in(bits, n_src)
+    V = bits.shape[0]
+    out = np.empty((V, row_bytes_for(m.shape[0])), dtype=np.uint8); counts = np.empty(V, dtype=np.int32)
+    _abi.check(_abi.load().sh_select_rows_host(bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], V, n_src, mp, int(m.shape[0]),
+                                               out.ctypes.data_as(_abi.c_u8p), counts.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out, counts
+
+
+__all__ = ["Engine", "Job", "PatternSet", "RowSelector", "hash_rows", "select_rows_host", "pack_variants", "row_bytes_for"]

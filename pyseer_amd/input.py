@@ -1497,7 +1497,8 @@ def iter_packed_blocks_native_multi(p, paths, min_af, max_af, block_size, want_p
 
 # ---------------------------------------------------------------------------------------------------------------
 # Packed cache: the parsed k-mer file as bit rows, so that further runs over the same samples (another phenotype column,
-# other covariates, LMM after fixed effects) skip gzip and text parsing and stream at the engine's rate.
+# other covariates, LMM after fixed effects) skip gzip and text parsing and stream at the engine's rate.  A run over a subset or another
+# order of the stored samples reads it too: iter_packed_blocks_cached(select=), whose rows are selected on the device (k_rows_select).
 #   header: b"SEERPK01", uint32 n_samples, uint32 row_bytes, uint64 len, sample names joined by "\n" (phenotype order)
 #   blocks: uint64 nv, uint64 name_bytes, int64 name_off[nv+1], int32 counts[nv], names, uint8 bits[nv*row_bytes]; nv = 0 ends
 # ---------------------------------------------------------------------------------------------------------------
@@ -1706,9 +1707,33 @@ class _DmaWindows(object):
                 self._kick()
 
 
-def check_packed_cache(p, path):
+def _cache_sample_map(stored, samples, select):
+    """The packed cache's stored sample names against the run's: None where they are the run's own list, else -- with `select` given and
+    SEERHIP_ROUTE cache_select not 0 -- the int32 table map[j] = position of run sample j among the stored names, for a cache whose names are
+    distinct and hold every run sample once.  Raises the ValueError every other cache has always met."""
+    if stored == samples:
+        return None
+    if select is not None and _route.route("cache_select") != "0" and len(set(stored)) == len(stored) and len(set(samples)) == len(samples):
+        where = {s: i for i, s in enumerate(stored)}
+        if all(s in where for s in samples):
+            return np.array([where[s] for s in samples], dtype=np.int32)
+    raise ValueError("packed cache was written for a different sample list / order (%d vs %d samples)" % (len(stored), len(samples)))
+
+
+def _open_selector(select, n_src, sample_map):
+    """rows -> (rows, counts) over the run's samples: on the device of the Engine `select` (k_rows_select), or by the host restatement
+    (select == "host", or SEERHIP_ROUTE cache_select=host); and what closes it."""
+    from . import engine as _engine
+    if select == "host" or _route.route("cache_select") == "host":
+        return (lambda bits: _engine.select_rows_host(bits, n_src, sample_map)), (lambda: None)
+    sel = _engine.RowSelector(select, n_src, sample_map)
+    return sel.select, sel.close
+
+
+def check_packed_cache(p, path, select=None):
     """The header checks of iter_packed_blocks_cached without reading a block (the library's own block loop, sh_job_run_packed, walks the file
-    itself): magic, sample list and order, row width.  Raises what the iterator raises."""
+    itself): magic, sample list and order, row width.  Raises what the iterator raises.  select (an Engine, "host", or anything but None):
+    a cache over a superset or another order of the samples is accepted as the iterator accepts it; returns its sample map, else None."""
     samples = [str(x) for x in p.index]
     with open(path, "rb") as f:
         head = f.read(24)
@@ -1720,15 +1745,19 @@ def check_packed_cache(p, path):
         if len(names) < int(ln):
             raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
     stored = names.decode().split("\n")
-    if stored != samples:
-        raise ValueError("packed cache was written for a different sample list / order (%d vs %d samples)" % (len(stored), len(samples)))
-    if int(rb) != row_bytes_for(len(samples)):
+    sample_map = _cache_sample_map(stored, samples, select)
+    if int(rb) != row_bytes_for(len(stored)):
         raise IOError("packed cache row width mismatch")
+    return sample_map
 
 
 def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, part=None, raw=False, device=None, ahead=2,
-                              say_empty=True):
+                              say_empty=True, select=None):
     """PackedBlock stream from a packed cache written by --save-packed; the samples (and their order) must be the run's own.
+    select: an Engine over the run's samples, or "host" -- a cache whose stored names are distinct and hold every run sample is accepted too:
+    every stored block's rows are restricted to the run's samples and brought into their order (engine.RowSelector on that engine's device;
+    "host": engine.select_rows_host) and its counts taken anew, on the reader thread, before blocks are merged; such rows are never handed
+    on as DMA windows.  A cache with the run's own list takes the path it always took.
     Stored blocks are re-cut to about `block_size` variants (stored blocks are never split, only merged).
     part = (i, n): only range i of n contiguous ranges of the cache's rows (the multi-GPU job: one range per device,
     pyseer_amd/__main__.py).  Ranges are made of whole blocks of the single stream, so the n parts yield exactly its blocks; they are
@@ -1761,12 +1790,14 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
         if pos > size:
             raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
         stored = mm[24:pos].decode().split("\n")
-        if stored != samples:
-            raise ValueError("packed cache was written for a different sample list / order (%d vs %d samples)"
-                             % (len(stored), n))
-        if int(rb) != row_bytes_for(n):
+        sample_map = _cache_sample_map(stored, samples, select)
+        if int(rb) != row_bytes_for(len(stored)):
             raise IOError("packed cache row width mismatch")
         rb = int(rb)
+        select_rows, select_close = (None, None) if sample_map is None else _open_selector(select, len(stored), sample_map)
+        use_dma = want_dma and sample_map is None
+        windows = _DmaWindows(device) if use_dma else None
+        windows_box.append(windows)
 
         def need(nbytes):
             nonlocal pos
@@ -1809,23 +1840,29 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
         if use_dma:
             windows.plan(np.frombuffer(mm, dtype=np.uint8, count=1).ctypes.data, extents, lo_blk, len(extents) if hi_blk is None else hi_blk)
         j = -1
-        while True:
-            at = need(16)
-            nv, nb = (int(x) for x in np.frombuffer(mm, dtype="<u8", count=2, offset=at))
-            if nv == 0:
-                return
-            j += 1
-            if hi_blk is not None and not (lo_blk <= j < hi_blk):                          # a stored block of another part: skipped unread
-                if j >= hi_blk:
+        try:
+            while True:
+                at = need(16)
+                nv, nb = (int(x) for x in np.frombuffer(mm, dtype="<u8", count=2, offset=at))
+                if nv == 0:
                     return
-                need(8 * (nv + 1) + 4 * nv + nb + nv * rb)
-                continue
-            off = np.frombuffer(mm, dtype="<i8", count=nv + 1, offset=need(8 * (nv + 1)))
-            counts = np.frombuffer(mm, dtype="<i4", count=nv, offset=need(4 * nv))
-            at = need(nb)
-            blob = np.frombuffer(mm, dtype=np.uint8, count=nb, offset=at) if raw else mm[at:at + nb]      # (raw: a view, the names are only read for printed rows)
-            bits = np.frombuffer(mm, dtype=np.uint8, count=nv * rb, offset=need(nv * rb)).reshape(nv, rb)
-            yield blob, off, counts, bits, j
+                j += 1
+                if hi_blk is not None and not (lo_blk <= j < hi_blk):                      # a stored block of another part: skipped unread
+                    if j >= hi_blk:
+                        return
+                    need(8 * (nv + 1) + 4 * nv + nb + nv * rb)
+                    continue
+                off = np.frombuffer(mm, dtype="<i8", count=nv + 1, offset=need(8 * (nv + 1)))
+                counts = np.frombuffer(mm, dtype="<i4", count=nv, offset=need(4 * nv))
+                at = need(nb)
+                blob = np.frombuffer(mm, dtype=np.uint8, count=nb, offset=at) if raw else mm[at:at + nb]  # (raw: a view, the names are only read for printed rows)
+                bits = np.frombuffer(mm, dtype=np.uint8, count=nv * rb, offset=need(nv * rb)).reshape(nv, rb)
+                if select_rows is not None:                                                # (the stored counts are those of the cache's samples)
+                    bits, counts = select_rows(bits)
+                yield blob, off, counts, bits, j
+        finally:
+            if select_close is not None:
+                select_close()
 
     def merged():
         acc, rows = [], 0
@@ -1837,12 +1874,14 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
         if acc:
             yield acc
 
-    use_dma = raw and device is not None and _route.route("dma", "1") != "0"
-    windows = _DmaWindows(device) if use_dma else None
+    want_dma = raw and device is not None and _route.route("dma", "1") != "0"
+    windows_box = []                     # the stream's DMA windows, or None: known once the header has been read (a selected cache has none)
 
     def finished():                      # merging and a block's host preparation (6 ms per 262 144 rows) on the reader's thread, ahead of the engine
+        windows = None
         try:
             for group in merged():
+                windows = windows_box[0]
                 if raw and len(group) == 1:
                     blob, off, counts, bits, j = group[0]
                     dma, release = windows.take(j) if windows is not None else (False, None)
@@ -1922,17 +1961,33 @@ def plan_packed_cache(options, p, var_file, read_first_block=True):
     return cache_stamp
 
 
-def open_kmer_block_stream(options, p, kmer_files, block_size):
+def announce_cache_select(p, path, select):
+    """--load-packed of the command line: the header checks (check_packed_cache), and for a cache over a superset or another order of the
+    run's samples the one line that says so.  Returns True for such a cache."""
+    sample_map = check_packed_cache(p, path, select=select)
+    if sample_map is None:
+        return False
+    with open(path, "rb") as f:
+        (stored,) = np.frombuffer(f.read(12), dtype="<u4", count=1, offset=8)
+    where = "host" if (select == "host" or _route.route("cache_select") == "host") else "device"
+    sys.stderr.write("pyseer_amd: packed cache holds %d samples; the run's %d are selected on the %s\n" % (int(stored), len(p), where))
+    return True
+
+
+def open_kmer_block_stream(options, p, kmer_files, block_size, select=None):
     """The RawBlock stream of a run that takes every parsed line as it is (--wg enet: the device applies its own rule), from what the
     command line names: --load-packed, --packed-cache, one or several --kmers files.  Returns (blocks, PackedCacheWriter or None): the
-    caller closes the writer once the stream has ended.  The cache is read through the page cache (device=None: no registered windows)."""
+    caller closes the writer once the stream has ended.  The cache is read through the page cache (device=None: no registered windows).
+    select: the run's Engine -- a --load-packed cache over a superset or another order of the samples is served through it."""
     cache_out = cache_stamp = None
     if not options.uncompressed and not options.load_packed:
         check_kmers_gzipped(kmer_files)
     if options.packed_cache and not options.load_packed and not options.save_packed:
         cache_stamp = plan_packed_cache(options, p, kmer_files[0], read_first_block=False)
     if options.load_packed:
-        return iter_packed_blocks_cached(p, options.load_packed, options.min_af, options.max_af, block_size, raw=True, device=None), None
+        if select is not None:
+            announce_cache_select(p, options.load_packed, select)
+        return iter_packed_blocks_cached(p, options.load_packed, options.min_af, options.max_af, block_size, raw=True, device=None, select=select), None
     if len(kmer_files) > 1:
         return iter_packed_blocks_native_multi(p, kmer_files, options.min_af, options.max_af, block_size, raw=True), None
     if options.save_packed:
