@@ -261,6 +261,27 @@ int64_t     sh_reader_par_chunks(sh_reader *r);
 sh_reader  *sh_reader_open_dev(sh_ctx *ctx, const char *path, const char *const *sample_names, int n_samples);
 int         sh_reader_dev_stats(sh_reader *r, int64_t *lines_dev, int64_t *lines_host, int64_t *bytes_up, int64_t *launches);
 double      sh_reader_dev_kernel_ms(sh_reader *r);
+/* Device inflate (csrc/inflate_dev.h, csrc/inflate_kernels.hip, csrc/inflate_api.inc).  Under SEERHIP_ROUTE kmer_inflate=1 a reader from
+ * sh_reader_open_dev has the members of a BGZF file decoded by k_bgzf_inflate, one launch per slab: the compressed bytes go up, the text
+ * comes back into the pinned slab for the host's CRC-32, newline index and names, and stays on the device for k_kmer_pack.  A member whose
+ * status, length or CRC-32 is wrong afterwards is decoded again on the host; errors read as on the host route.  Other containers are read
+ * as without the key.
+ * sh_inflate_host: one raw-DEFLATE member by the host build of the kernel's decoder: [cdata, cdata + clen) into [out, out + isize).
+ * Returns 0, a positive ShInfStatus of csrc/inflate_dev.h (malformed input; nothing outside either range was touched), or SH_EINVAL.
+ * sh_inflate_members_dev: n members through the kernel in one launch, host memory in and out.  Member i is comp[coff[i] .. + clen[i]) and
+ * decodes to out[ooff[i] .. + isize[i]) (isize <= 65536); `out` goes up as it is and comes back with min(produced, isize) bytes of every
+ * member written and no other byte changed.  status[i], produced[i] as sh_inflate_host gives them; kernel_ms (may be NULL): the kernel's
+ * time by stream events.
+ * sh_reader_dev_inflate_stats: members decoded by the kernel (without a context: by the host build) / decoded again by the host decoder,
+ * bytes sent up (compressed members and their table) and brought back (text and statuses), the kernel's time so far.  All zero where the
+ * key is not set or the file is not BGZF.
+ * sh_reader_set_inflate: what the calling thread's NEXT sh_reader_open_dev does, whatever the route key says: 1 the device inflate, 0 not,
+ * negative as the key says (the state after every open).  Thread-local, so that a caller need not touch the environment. */
+void        sh_reader_set_inflate(int on);
+int         sh_inflate_host(const uint8_t *cdata, int64_t clen, uint8_t *out, int64_t isize, int64_t *produced);
+int         sh_inflate_members_dev(sh_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const int64_t *coff, const int32_t *clen, const int32_t *isize,
+                                   const int64_t *ooff, int64_t n, uint8_t *out, int64_t out_bytes, int32_t *status, int32_t *produced, double *kernel_ms);
+int         sh_reader_dev_inflate_stats(sh_reader *r, int64_t *members_dev, int64_t *members_host, int64_t *bytes_up, int64_t *bytes_down, double *kernel_ms);
 
 /* introspection: how many variants of the LAST batch went through the Firth kernel / its pinv slow path */
 int sh_glm_info(sh_ctx *ctx, int64_t *firth_routed, int64_t *pinv_routed);

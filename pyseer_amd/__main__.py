@@ -11,7 +11,8 @@ tested ones -- fit_lmm returns them that way, lmm.py:160-224).
 without covariates: up to 1023 clusters).
 
 K-mer text goes through the native reader (csrc/reader.cpp), whose parser reads the sample tokens on the host; --device-reader (one file, one
-device) has them read on the device instead (k_kmer_pack), same bytes out; every other route ignores the flag.
+device) has them read on the device instead (k_kmer_pack), same bytes out; every other route ignores the flag.  --device-inflate implies it and
+has the members of a BGZF file decoded on the device too (k_bgzf_inflate); for any other container it is --device-reader.
 
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
 reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or
@@ -190,6 +191,9 @@ def get_options(argv=None):
     ot.add_argument('--device-reader', action='store_true', default=False,
                     help='Read the sample tokens of one --kmers file on the device (the native reader; containers, lines and names stay on the host); '
                          'ignored where another reader is used')
+    ot.add_argument('--device-inflate', action='store_true', default=False,
+                    help='Decode the members of a BGZF (bgzip) --kmers file on the device as well; implies --device-reader and is ignored where '
+                         'that is ignored; for any other container it is --device-reader')
     ot.add_argument('--python-sink', action='store_true', default=False,
                     help='Format every output row in Python (one result tuple per variant) instead of the native block sink')
     ot.add_argument('--serial-sink', action='store_true', default=False,
@@ -543,10 +547,13 @@ def main(argv=None):
         if options.save_packed:
             cache_out = PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
         # --device-reader (SEERHIP_ROUTE kmer_dev=1): the sample tokens are read on the first context's device, on a stream of the reader's own
-        dev_reader = (options.device_reader or _route.route("kmer_dev", "0") == "1") and options.gpus is None and bool(engs)
+        # --device-inflate (SEERHIP_ROUTE kmer_inflate=1): that reader's BGZF members are decoded there too, on another stream of its own
+        dev_inflate = options.device_inflate or _route.route("kmer_inflate", "0") == "1"
+        dev_reader = (options.device_reader or dev_inflate or _route.route("kmer_dev", "0") == "1") and options.gpus is None and bool(engs)
         blocks = iter_packed_blocks_native(p, var_file, options.min_af, options.max_af, job_block,
                                            want_patterns=want_pat, want_samples=options.print_samples,
-                                           save_to=cache_out, raw=job_path, engine=(engs[0] if dev_reader else None))
+                                           save_to=cache_out, raw=job_path, engine=(engs[0] if dev_reader else None),
+                                           inflate=(True if options.device_inflate else None))
     elif native_vcf:
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
         blocks = iter_packed_blocks_vcf_native(p, var_file, engs[0], options.min_af, options.max_af, options.max_missing, options.block_size,

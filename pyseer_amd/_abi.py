@@ -67,6 +67,12 @@ SIGNATURES = {
     "sh_reader_open_dev": (C.c_void_p, [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
     "sh_reader_dev_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sh_reader_dev_kernel_ms": (C.c_double, [C.c_void_p]),
+    # device inflate of BGZF members (csrc/inflate_dev.h, csrc/inflate_kernels.hip, csrc/inflate_api.inc)
+    "sh_reader_set_inflate": (None, [C.c_int]),
+    "sh_inflate_host": (C.c_int, [c_u8p, C.c_int64, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
+    "sh_inflate_members_dev": (C.c_int, [C.c_void_p, c_u8p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64), C.c_int64, c_u8p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_dp]),
+    "sh_reader_dev_inflate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_dp]),
     "sh_format_rows": (C.c_int64, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(c_dp), C.c_int, c_dp,
                                    C.c_int, c_u8p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.c_int, c_u32p, C.c_char_p,
                                    C.c_int64]),

@@ -25,6 +25,7 @@
 #include "rtab_kernels.h"
 #include "rtab_reader.h"
 #include "kmer_kernels.h"
+#include "inflate_dev.h"
 #include "reader_dev.h"
 #include <unordered_map>
 #include "enet_params.h"
@@ -1179,6 +1180,7 @@ int sh_sim_finish(sh_ctx *c, double *K)
 #include "vcf_api.inc"
 #include "rtab_api.inc"
 #include "kmer_api.inc"
+#include "inflate_api.inc"
 #include "enet_api.inc"
 #include "select_api.inc"
 

@@ -28,7 +28,16 @@ struct KmerDev {
     int64_t lines_dev = 0, lines_host = 0, bytes_up = 0, launches = 0;
     // where the consumer's time goes (SEERHIP_DEBUG=host: one line on stderr when the reader closes), ns
     int64_t ns_in = 0, ns_out = 0, ns_pack = 0, ns_wait = 0;
+    // ---- device inflate (inflate_api.inc; SEERHIP_ROUTE kmer_inflate=1): the decoding thread runs k_bgzf_inflate on a stream of its own and
+    // leaves the slab's device copy in `inflated` for slab_in to bind; `mu` guards `spare` and `inflated`, which both threads touch
+    std::mutex mu; std::unordered_map<const char *, Copy> inflated;
+    hipStream_t istream = nullptr; hipEvent_t i0 = nullptr, i1 = nullptr;
+    uint8_t *h_comp = nullptr, *d_comp = nullptr; size_t cap_comp = 0;       // the members' deflate bodies, one after the other
+    uint8_t *h_mem = nullptr, *d_mem = nullptr; int64_t cap_mem = 0;         // [n] ShInfMember up; [n] status, [n] produced back
+    std::atomic<int64_t> members_dev{0}, members_host{0};                    // (the consumer moves a member decoded again from one to the other)
+    std::atomic<int64_t> infl_up{0}, infl_down{0}; std::atomic<double> infl_ms{0.0};      // (written by the decoding thread alone)
 };
+static bool kmer_inflate(void *self, char *buf, size_t pad, ShReaderMember *mem, int64_t n, std::string &err);      // inflate_api.inc
 
 static inline int64_t kmer_now_ns() { return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 struct KmerTimer { int64_t &acc; int64_t t0; explicit KmerTimer(int64_t &a) : acc(a), t0(kmer_now_ns()) {} ~KmerTimer() { acc += kmer_now_ns() - t0; } };
@@ -59,18 +68,36 @@ static void kmer_release(void *self, char *buf)
     hipHostFree(buf);
 }
 
+// the device copy for the slab in `buf`: the one the inflate hook left for it, a spare one, or a new one
+static bool kmer_copy_take(KmerDev *k, const char *buf, KmerDev::Copy &c, std::string &err)
+{
+    {
+        std::lock_guard<std::mutex> lk(k->mu);
+        const auto it = k->inflated.find(buf);
+        if (it != k->inflated.end()) { c = it->second; k->inflated.erase(it); return true; }
+        if (!k->spare.empty()) { c = k->spare.back(); k->spare.pop_back(); return true; }
+    }
+    if (!kmer_hip(hipMalloc((void **)&c.d, k->buf_bytes.load() + KMER_SLACK), "hipMalloc (slab)", err)) return false;
+    if (!kmer_hip(hipEventCreateWithFlags(&c.up, hipEventDisableTiming), "hipEventCreate", err)) { hipFree(c.d); c.d = nullptr; return false; }
+    return true;
+}
+
 static bool kmer_slab_in(void *self, const char *buf, size_t from, size_t to, std::string &err)
 {
     KmerDev *k = (KmerDev *)self;
-    if (!k->ctx) return true;
+    // a second call for a slab in hand: a member of an inflated slab that the reader decoded again
+    const auto again = k->bound.find(buf);
+    if (again != k->bound.end()) { k->members_host += 1; k->members_dev -= 1; }
+    if (!k->ctx) {                                         // (without a device only the inflate hook's slabs are kept track of, for that count)
+        std::lock_guard<std::mutex> lk(k->mu);
+        if (k->inflated.erase(buf)) k->bound[buf] = KmerDev::Copy();
+        return true;
+    }
     KmerTimer tm(k->ns_in);
     if (!kmer_hip(hipSetDevice(k->device), "hipSetDevice", err)) return false;
     KmerDev::Copy c;
-    if (!k->spare.empty()) { c = k->spare.back(); k->spare.pop_back(); }
-    else {
-        if (!kmer_hip(hipMalloc((void **)&c.d, k->buf_bytes.load() + KMER_SLACK), "hipMalloc (slab)", err)) return false;
-        if (!kmer_hip(hipEventCreateWithFlags(&c.up, hipEventDisableTiming), "hipEventCreate", err)) { hipFree(c.d); return false; }
-    }
+    if (again != k->bound.end()) c = again->second;
+    else if (!kmer_copy_take(k, buf, c, err)) return false;
     k->bound[buf] = c;
     if (to > from && !kmer_hip(hipMemcpyAsync(c.d + from, buf + from, to - from, hipMemcpyHostToDevice, k->stream), "hipMemcpyAsync (slab)", err)) return false;
     if (!kmer_hip(hipEventRecord(c.up, k->stream), "hipEventRecord", err)) return false;
@@ -81,13 +108,18 @@ static bool kmer_slab_in(void *self, const char *buf, size_t from, size_t to, st
 static void kmer_slab_out(void *self, const char *buf)
 {
     KmerDev *k = (KmerDev *)self;
-    if (!k->ctx) return;
+    {                                                      // (a slab that failed before slab_in: what the inflate hook left for it)
+        std::lock_guard<std::mutex> lk(k->mu);
+        const auto left = k->inflated.find(buf);
+        if (left != k->inflated.end()) { if (left->second.d) k->spare.push_back(left->second); k->inflated.erase(left); }
+    }
     auto it = k->bound.find(buf);
     if (it == k->bound.end()) return;
+    if (!k->ctx) { k->bound.erase(it); return; }
     KmerTimer tm(k->ns_out);
     hipSetDevice(k->device);
     hipEventSynchronize(it->second.up);                    // the pinned buffer is written again from here on
-    k->spare.push_back(it->second);
+    { std::lock_guard<std::mutex> lk(k->mu); k->spare.push_back(it->second); }
     k->bound.erase(it);
 }
 
@@ -201,7 +233,15 @@ static void kmer_destroy(void *self)
     if (k->ctx) {
         hipSetDevice(k->device);
         if (k->stream) hipStreamSynchronize(k->stream);
+        if (k->istream) hipStreamSynchronize(k->istream);
         for (auto &b : k->bound) k->spare.push_back(b.second);
+        for (auto &b : k->inflated) k->spare.push_back(b.second);
+        if (k->h_comp) hipHostFree(k->h_comp);
+        if (k->h_mem) hipHostFree(k->h_mem);
+        hipFree(k->d_comp); hipFree(k->d_mem);
+        if (k->i0) hipEventDestroy(k->i0);
+        if (k->i1) hipEventDestroy(k->i1);
+        if (k->istream) hipStreamDestroy(k->istream);
         for (auto &c : k->spare) { hipFree(c.d); if (c.up) hipEventDestroy(c.up); }
         if (k->h_tab) hipHostFree(k->h_tab);
         if (k->h_rows) hipHostFree(k->h_rows);
@@ -259,8 +299,14 @@ static int kmer_open_device(KmerDev *k)
     return SH_OK;
 }
 
+// what sh_reader_set_inflate asked of the calling thread's next sh_reader_open_dev: -1 as the route key says, 0 off, 1 on
+static thread_local int g_kmer_inflate = -1;
+void sh_reader_set_inflate(int on) { g_kmer_inflate = on < 0 ? -1 : (on ? 1 : 0); }
+
 sh_reader *sh_reader_open_dev(sh_ctx *ctx, const char *path, const char *const *sample_names, int n_samples)
 {
+    const int asked = g_kmer_inflate;
+    g_kmer_inflate = -1;                                   // (it holds for one open, whatever becomes of it)
     auto refuse = [](int code, const std::string &msg) -> sh_reader * { fail(code, msg); sh_reader_set_error(msg.c_str()); return nullptr; };
     if (!path || !sample_names || n_samples < 1) return refuse(SH_EINVAL, "bad argument");
     if (ctx && ctx->N != n_samples) return refuse(SH_ESHAPE, "the context was created for another number of samples");
@@ -274,6 +320,10 @@ sh_reader *sh_reader_open_dev(sh_ctx *ctx, const char *path, const char *const *
     }
     ShReaderHooks h;
     h.self = k; h.alloc = kmer_alloc; h.release = kmer_release; h.slab_in = kmer_slab_in; h.slab_out = kmer_slab_out; h.pack = kmer_pack; h.destroy = kmer_destroy;
+    // SEERHIP_ROUTE kmer_inflate=1, or sh_reader_set_inflate before this call on this thread: the members of a BGZF file are decoded by
+    // k_bgzf_inflate (without a context: by the host build of its core)
+    const char *ki = sh_route("kmer_inflate");
+    if (asked == 1 || (asked < 0 && ki && std::string(ki) == "1")) h.inflate = kmer_inflate;
     sh_reader *r = sh_reader_open_hooked(path, sample_names, n_samples, h);      // (owns k from here on)
     if (!r) fail(SH_EINVAL, sh_reader_error());
     return r;

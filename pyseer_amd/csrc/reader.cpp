@@ -117,6 +117,8 @@ struct Slab {
     bool last = false; std::string err;
     std::vector<MemberEndAt> ends;                              // gzip members that end inside this slab: offset, CRC-32 of the trailer
     std::vector<uint32_t> nl; bool indexed = false;             // offsets of the newlines in data[0 .. len) (index_newlines, on first use)
+    // the hooks' inflate decoded this slab: its text is on the device already, but for the carried tail and these ranges (of mem, decoded again here)
+    bool dev_text = false; std::vector<std::pair<size_t, size_t>> redone;
 };
 
 struct sh_reader {
@@ -527,15 +529,35 @@ static void produce_bgzf(sh_reader *r)
         memcpy(buf + PAD - tail.size(), tail.data(), tail.size());
         Slab sl; sl.mem = buf; sl.data = buf + PAD; sl.pad = tail.size(); sl.len = total;
         std::atomic<int> bad{0};
-        r->pool_bgzf->run((int64_t)mem.size(), 4, [&](int64_t i) {
+        const auto decode = [&](int64_t i) -> bool {
             static thread_local std::vector<uint8_t> tmp(65536 + 512);
             static thread_local shinf::Decoder d;
             const Mem &m = mem[(size_t)i];
             d.begin(m.cdata, m.cdata + m.clen, true);
             uint8_t *o = d.run(tmp.data(), tmp.data() + tmp.size(), tmp.data());
-            if (d.state != shinf::Decoder::DONE || (size_t)(o - tmp.data()) != m.isize || shcrc::crc32(0u, tmp.data(), m.isize) != m.crc) ++bad;
-            else memcpy(buf + PAD + m.off, tmp.data(), m.isize);
-        });
+            if (d.state != shinf::Decoder::DONE || (size_t)(o - tmp.data()) != m.isize || shcrc::crc32(0u, tmp.data(), m.isize) != m.crc) return false;
+            memcpy(buf + PAD + m.off, tmp.data(), m.isize);
+            return true;
+        };
+        if (r->hooked && r->hooks.inflate) {
+            // the hooks decode the slab's members in one go; the pool checks every CRC-32 over what came back and decodes again what is not right
+            std::vector<ShReaderMember> hm(mem.size());
+            for (size_t i = 0; i < mem.size(); ++i) hm[i] = ShReaderMember{mem[i].cdata, (uint32_t)mem[i].clen, mem[i].isize, mem[i].off, -1, 0u};
+            std::string herr;
+            if (!r->hooks.inflate(r->hooks.self, buf, PAD, hm.data(), (int64_t)hm.size(), herr)) { if (err.empty()) err = herr; }
+            else {
+                std::vector<uint8_t> again(mem.size(), 0);
+                r->pool_bgzf->run((int64_t)mem.size(), 4, [&](int64_t i) {
+                    const Mem &m = mem[(size_t)i];
+                    if (hm[(size_t)i].status == 0 && hm[(size_t)i].produced == m.isize && shcrc::crc32(0u, (const uint8_t *)buf + PAD + m.off, m.isize) == m.crc) return;
+                    if (decode(i)) again[(size_t)i] = 1; else ++bad;
+                });
+                sl.dev_text = true;
+                for (size_t i = 0; i < mem.size(); ++i) if (again[i]) sl.redone.emplace_back(mem[i].off, mem[i].off + mem[i].isize);
+            }
+        } else {
+            r->pool_bgzf->run((int64_t)mem.size(), 4, [&](int64_t i) { if (!decode(i)) ++bad; });
+        }
         if (bad && err.empty()) err = "BGZF: a member failed to decode or its CRC-32 check";
         sl.err = err; sl.last = p >= end || !err.empty();
         keep_tail(tail, PAD, sl.data, sl.len);
@@ -645,7 +667,10 @@ static bool next_slab(sh_reader *r, bool *failed)
     if (!sl.err.empty()) { g_rerr = sl.err; *failed = true; r->eof = true; release_slab(r, sl); return false; }
     if (r->hooked && sl.mem) {
         std::string err;
-        if (!r->hooks.slab_in(r->hooks.self, sl.mem, r->pad_bytes - sl.pad, r->pad_bytes + sl.len, err)) { g_rerr = err; *failed = true; r->eof = true; release_slab(r, sl); return false; }
+        // (a slab the hooks inflated: the carried tail, then what was decoded again here)
+        bool ok = r->hooks.slab_in(r->hooks.self, sl.mem, r->pad_bytes - sl.pad, r->pad_bytes + (sl.dev_text ? 0 : sl.len), err);
+        for (size_t i = 0; ok && i < sl.redone.size(); ++i) ok = r->hooks.slab_in(r->hooks.self, sl.mem, r->pad_bytes + sl.redone[i].first, r->pad_bytes + sl.redone[i].second, err);
+        if (!ok) { g_rerr = err; *failed = true; r->eof = true; release_slab(r, sl); return false; }
     }
     if (sl.last) r->eof = true;
     r->held.push_back(std::move(sl));

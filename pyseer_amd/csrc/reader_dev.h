@@ -13,6 +13,12 @@ struct ShReaderLine {
     const char *buf;                    // the slab buffer (as `alloc` returned it) the line lies in, or nullptr: in no slab (a line longer than the pad, reader=zlib)
 };
 
+// a BGZF member of a slab for `inflate`: its deflate body, and where its text goes (buf + pad + off); the hook fills in the last two
+struct ShReaderMember {
+    const uint8_t *cdata; uint32_t clen, isize; size_t off;
+    int32_t status; uint32_t produced;     // 0 and isize: the text is there (the reader still checks its CRC-32)
+};
+
 struct ShReaderHooks {
     void *self = nullptr;
     char *(*alloc)(void *self, size_t bytes) = nullptr;                  // a slab buffer (called on the decoding thread)
@@ -22,6 +28,10 @@ struct ShReaderHooks {
     void (*slab_out)(void *self, const char *buf) = nullptr;
     // rows and counts of `n` lines (bits is zeroed, row_bytes * 8 >= the sample count)
     bool (*pack)(void *self, const ShReaderLine *lines, int64_t n, uint8_t *bits, int64_t row_bytes, int32_t *counts, std::string &err) = nullptr;
+    // optional (BGZF only): decode the `n` members of a slab into `buf` instead of the reader's decoding threads, once per slab, on the decoding
+    // thread.  A member whose status, length or CRC-32 is wrong afterwards is decoded again by the reader; slab_in is then called with
+    // [pad - carried tail, pad) first and once more for the range of every member decoded again.  false: the slab fails with `err`
+    bool (*inflate)(void *self, char *buf, size_t pad, ShReaderMember *mem, int64_t n, std::string &err) = nullptr;
     void (*destroy)(void *self) = nullptr;                               // after the last buffer was released
 };
 

@@ -51,6 +51,9 @@
 //   cache_select=0|host [unset] a packed cache whose samples are a superset or another order of the run's (input.py iter_packed_blocks_cached):
 //                    unset, its rows are restricted and permuted on the device (k_rows_select); host, by the host restatement
 //                    (sh_select_rows_host); 0, such a cache is refused as a cache of other samples always was
+//   kmer_inflate=1   [0]  a reader opened by sh_reader_open_dev has the members of a BGZF file decoded by k_bgzf_inflate (inflate_kernels.hip; without
+//                    a context by the host build of the same decoder, inflate_dev.h) instead of its decoding threads, as --device-inflate asks;
+//                    on the command line it implies kmer_dev=1
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -60,7 +63,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

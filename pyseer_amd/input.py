@@ -783,10 +783,12 @@ class NativeKmerReader(object):
     gzip inflate + tokenise + sample lookup + bit packing in C++ (OpenMP over the lines of a block).  No GPU needed.
     engine: an Engine selects the device route (sh_reader_open_dev): the same containers, framing and names on the host, the sample tokens
     read by k_kmer_pack on the engine's device, on a stream of the reader's own.  DEVICE_HOST_RULE instead of an engine selects the
-    library's host restatement of that kernel (checks without a device).  The blocks are the same arrays either way."""
+    library's host restatement of that kernel (checks without a device).  The blocks are the same arrays either way.
+    inflate (device route only): True has the members of a BGZF file decoded by k_bgzf_inflate on the engine's device (DEVICE_HOST_RULE: by the
+    host build of the same decoder), False never, None as SEERHIP_ROUTE kmer_inflate says; other containers are read as without it."""
     DEVICE_HOST_RULE = "device-route-host-rule"
 
-    def __init__(self, path, sample_names, block_size=3000, max_name=256, engine=None):
+    def __init__(self, path, sample_names, block_size=3000, max_name=256, engine=None, inflate=None):
         import ctypes as C
         from . import _abi
         self._C, self._abi = C, _abi
@@ -799,6 +801,8 @@ class NativeKmerReader(object):
         if engine is None:
             h = self._lib.sh_reader_open(str(path).encode(), arr, self.n)
         else:
+            if inflate is not None:                         # (for this thread's next open only; the environment is not touched)
+                self._lib.sh_reader_set_inflate(1 if inflate else 0)
             h = self._lib.sh_reader_open_dev(self._engine._h if self._engine is not None else None, str(path).encode(), arr, self.n)
         if not h:
             raise IOError(self._lib.sh_reader_error().decode())
@@ -827,6 +831,15 @@ class NativeKmerReader(object):
         self._abi.check(self._lib.sh_reader_dev_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"lines_dev": a.value, "lines_host": b.value, "bytes_up": c.value, "launches": d.value,
                 "kernel_ms": float(self._lib.sh_reader_dev_kernel_ms(self._h))}
+
+    def inflate_stats(self):
+        """The device inflate's counters (sh_reader_dev_inflate_stats): BGZF members decoded by the kernel (DEVICE_HOST_RULE: by the host build of
+        its decoder) / decoded again by the host decoder, bytes sent up and brought back, and the kernel's own time in ms.  All zero where
+        the route is off or the file is not BGZF."""
+        C = self._C
+        a, b, c, d, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._abi.check(self._lib.sh_reader_dev_inflate_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(ms)))
+        return {"members_dev": a.value, "members_host": b.value, "bytes_up": c.value, "bytes_down": d.value, "kernel_ms": ms.value}
 
     def raw_blocks(self):
         """(bits, counts, names_blob, name_off) per block; names stay one bytes blob + offsets (what the block sink consumes)."""
@@ -1398,14 +1411,15 @@ def _block_from_raw(n, samples, order, names, blob, off, bits, counts, min_af, m
 
 
 def iter_packed_blocks_native(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, save_to=None, raw=False, say_empty=True,
-                              engine=None):
+                              engine=None, inflate=None):
     """Same PackedBlock stream as iter_packed_blocks for k-mer files, fed by the native reader.  save_to: a PackedCacheWriter that
     receives every raw block (all parsed variants, before the AF filter).  raw: RawBlock objects for the job stream instead.
-    engine: the sample tokens are read on that engine's device (NativeKmerReader, --device-reader); the blocks are the same."""
+    engine: the sample tokens are read on that engine's device (NativeKmerReader, --device-reader); the blocks are the same.
+    inflate: with an engine, a BGZF file's members are decoded there too (--device-inflate); None: as SEERHIP_ROUTE kmer_inflate says."""
     samples = [str(x) for x in p.index]
     order = sorted(range(len(samples)), key=lambda i: samples[i])
     n = len(samples)
-    reader = NativeKmerReader(path, samples, block_size, engine=engine)
+    reader = NativeKmerReader(path, samples, block_size, engine=engine, inflate=inflate)
     def finished():                      # the whole of a block's host preparation runs on the reader's thread, ahead of the engine
         for bits, counts, blob, off in reader.raw_blocks():
             if save_to is not None:

@@ -33,6 +33,8 @@ def get_options(argv=None):
                         help='Parse k-mer, VCF and Rtab files with the Python reader instead of the native one')
     parser.add_argument('--device-reader', action='store_true', default=False,
                         help='Read the sample tokens of a --kmers file on the device (the native reader); ignored with --python-reader, --vcf and --pres')
+    parser.add_argument('--device-inflate', action='store_true', default=False,
+                        help='Decode the members of a BGZF (bgzip) --kmers file on the device as well; implies --device-reader and is ignored where that is')
     parser.add_argument('--version', action='version', version='%(prog)s ' + __version__)
     return parser.parse_args(argv)
 
@@ -82,12 +84,12 @@ class SimilarityAccumulator(object):
 
 
 def similarity_matrix(p, var_type, infile, path, all_strains, sample_order, min_af, max_af, max_missing, uncompressed,
-                      device=0, python_reader=False, progress=None, device_reader=False):
+                      device=0, python_reader=False, progress=None, device_reader=False, device_inflate=None):
     """The loop of similarity.py:99-113 over PackedBlocks."""
     from .input import iter_packed_blocks, iter_packed_blocks_native, iter_packed_blocks_rtab_native, iter_packed_blocks_vcf_native
     acc = SimilarityAccumulator(len(p), device=device)
     if var_type == "kmers" and not python_reader:
-        blocks = iter_packed_blocks_native(p, path, min_af, max_af, block_size, engine=(acc.engine if device_reader else None))
+        blocks = iter_packed_blocks_native(p, path, min_af, max_af, block_size, engine=(acc.engine if device_reader else None), inflate=device_inflate)
     elif var_type == "vcf" and not python_reader:       # the sample columns are tokenised on the accumulator's device (pyseer/similarity.py:86-88)
         blocks = iter_packed_blocks_vcf_native(p, path, acc.engine, min_af, max_af, max_missing, block_size, want_patterns=False)
     elif var_type == "Rtab" and not python_reader:      # the calls likewise (k_rtab_pack)
@@ -142,7 +144,9 @@ def main(argv=None):
     K = similarity_matrix(p, var_type, infile, path, all_strains, sample_order, options.min_af, options.max_af,
                           options.max_missing, options.uncompressed, device=options.gpu,
                           python_reader=options.python_reader,
-                          device_reader=(options.device_reader or _route.route("kmer_dev", "0") == "1"),
+                          device_reader=(options.device_reader or options.device_inflate or _route.route("kmer_dev", "0") == "1"
+                                         or _route.route("kmer_inflate", "0") == "1"),
+                          device_inflate=(True if options.device_inflate else None),
                           progress=lambda n: sys.stderr.write('Matrix size ' + str(n) + '\n'))
     sys.stderr.write("Calculating sample similarity\n")
     pd.DataFrame(K, index=p.index, columns=p.index).to_csv(sys.stdout, sep='\t')
