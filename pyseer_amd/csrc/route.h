@@ -36,7 +36,7 @@
 //                    k_lmm_ragged_i8 (N mod 128 in 1 .. LMM_RAGGED_MAX)
 //   lanes=n          [3]  lanes of a fixed-effects context (sh_set_lanes overrides)
 //   reader=serial|zlib [par] container decoder of the native reader;  reader_threads=T  its parser workers
-//   wait=spin        [sleep], job=0 / py [1], dma=0 [1], procs=0 [1]   command line (pyseer_amd/__main__.py, input.py): host threads spin on the device; the
+//   wait=spin        [sleep], job=0 / py [1], dma=0 [1], procs=0 [1]   command line (pyseer_amd/cli_run.py, input.py): host threads spin on the device; the
 //                    Python block loop instead of the job stream; rows through pinned slabs instead of DMA from the registered cache mapping
 //   dma_window=B     [1 GB] bytes of the packed-cache mapping registered for DMA at a time by the library's block loop (job_run.inc; small values:
 //                    many windows in a small cache)
