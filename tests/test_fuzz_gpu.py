@@ -211,6 +211,18 @@ def test_forced_firth_random_configurations(seed):
     assert good.all(), (N, q, np.argwhere(~good)[:4].tolist())
 
 
+_WIDE_SEEDS = (0, 1, 2)       # their wide draws have estimable null models: tests/test_glm_wide_cases_cpu.py
+
+
+@pytest.mark.parametrize("kind", ["fixed", "firth"])
+@pytest.mark.parametrize("seed", _WIDE_SEEDS)
+def test_wide_random_configurations(seed, kind, monkeypatch):
+    """The wide draw of the two case builders (FUZZ_WIDE: q in 15 .. 32 on the run-time-width kernels of glm_wide.hip, forced Firth
+    included) in the default suite, held as the two tests above hold their cases."""
+    monkeypatch.setenv("FUZZ_WIDE", "1")
+    (test_fixed_effects_random_configurations if kind == "fixed" else test_forced_firth_random_configurations)(seed)
+
+
 @pytest.mark.parametrize("seed", _SEEDS)
 def test_lineage_random_configurations(seed):
     """fit_lineage_effect (pyseer/model.py:151-199) for random sample counts, lineage widths on both sides of the fixed-width /
