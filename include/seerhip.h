@@ -224,6 +224,17 @@ int sh_sim_begin(sh_ctx *ctx);
 int sh_sim_accumulate(sh_ctx *ctx, const uint8_t *bits, int64_t row_bytes, int64_t V);
 int sh_sim_accumulate_dev(sh_ctx *ctx, const void *d_bits, int64_t row_bytes, int64_t V);
 int sh_sim_finish(sh_ctx *ctx, double *K);
+/* The matrix as the text the reference prints: pd.DataFrame(K, index=names, columns=names).to_csv(sep='\t') (pyseer/similarity.py:116), made
+ * on the device (csrc/simtext_kernels.hip k_sim_text_len, k_sim_format).  K == NULL: the accumulated matrix of sh_sim_begin/accumulate; else a
+ * host N x N row-major matrix, which is uploaded.  names + names_off[j] .. names_off[j + 1]: the name of sample j (N + 1 offsets, UTF-8 bytes as
+ * they are printed; a name with a tab, a double quote or a line end is refused: the reference's writer would quote it).  nan_mask (NULL: none):
+ * N bytes; every cell in the row or the column of a flagged sample is an empty field, as a NaN is.  A header line (an empty first field, the
+ * names), one line per sample (its name, then every value as its decimal integer and ".0"), tab-separated, "\n" line ends.
+ * *len is always set to the text's length; the text is written only where out != NULL and cap >= *len (out == NULL or a smaller cap: the
+ * length query, SH_OK, nothing written).  Lengths and offsets are 64-bit.  A value the notation cannot express -- a non-integer (or a NaN
+ * outside nan_mask), a negative (-0.0 too), anything >= 1e15 -- is refused with SH_EINVAL and sh_last_error names the case. */
+int sh_sim_text(sh_ctx *ctx, const double *K, const char *names, const int64_t *names_off, const uint8_t *nan_mask, uint8_t *out, int64_t cap,
+                int64_t *len);
 
 /* ---------------------------------------------------------------------------------------------
  * Native k-mer text reader / packer (host code; replaces the k-mer branch of pyseer/input.py:301 read_variant for the GPU
@@ -575,6 +586,10 @@ void        sh_nameset_free(sh_nameset *set);
  *     returns.  src_is_dma != 0: `bits` lies in memory the device may read where it is (sh_host_register); out_bits may be any host memory.
  *   rows_dev: the same with rows, output and counts in device memory (8-byte aligned), on the selector's stream; complete at return.
  *   rows_host: the rule restated in plain C++ on the host pool, no context and no device: checks, and the rate to compare against.
+ *   sh_sim_accumulate_select: V host rows of the source width into the similarity accumulator of the selector's context (sh_sim_begin has
+ *     run): staged through the selector's pinned memory, uploaded and selected on its stream, accumulated on the context's as
+ *     sh_sim_accumulate_dev does (sh_set_af_filter applies to the counts over the n_dst samples); the two streams are ordered by events.
+ *     Every row crosses to the device once and none comes back.  Complete when the call returns.
  * One thread per selector at a time.
  * ------------------------------------------------------------------------------------------- */
 typedef struct sh_select sh_select;
@@ -584,6 +599,7 @@ int         sh_select_rows(sh_select *s, const uint8_t *bits, int64_t src_row_by
 int         sh_select_rows_dev(sh_select *s, const void *d_bits, int64_t src_row_bytes, int64_t V, void *d_out, int32_t *d_counts);
 int         sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits,
                                 int32_t *out_counts);
+int         sh_sim_accumulate_select(sh_ctx *ctx, sh_select *sel, const uint8_t *bits, int64_t src_row_bytes, int64_t V);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,7 @@ SIGNATURES = {
     "sh_sim_accumulate": (C.c_int, [C.c_void_p, c_u8p, C.c_int64, C.c_int64]),
     "sh_sim_accumulate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "sh_sim_finish": (C.c_int, [C.c_void_p, c_dp]),
+    "sh_sim_text": (C.c_int, [C.c_void_p, c_dp, C.c_char_p, C.POINTER(C.c_int64), c_u8p, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
     "sh_reader_open": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
     "sh_reader_set_concurrency": (None, [C.c_int]),
     "sh_reader_close": (None, [C.c_void_p]),
@@ -160,6 +161,7 @@ SIGNATURES = {
     "sh_select_rows": (C.c_int, [C.c_void_p, c_u8p, C.c_int64, C.c_int64, c_u8p, C.POINTER(C.c_int32), C.c_int]),
     "sh_select_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "sh_select_rows_host": (C.c_int, [c_u8p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, c_u8p, C.POINTER(C.c_int32)]),
+    "sh_sim_accumulate_select": (C.c_int, [C.c_void_p, C.c_void_p, c_u8p, C.c_int64, C.c_int64]),
 }
 
 

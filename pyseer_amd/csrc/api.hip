@@ -34,6 +34,9 @@ extern "C" {
 hipError_t shk_sim_accumulate(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, int NB64, double min_af, double max_af,
                               int af_on, uint64_t *keep, uint64_t *S, int NS, unsigned long long *Kacc);
 hipError_t shk_sim_finish(hipStream_t st, const unsigned long long *Kacc, int NS, int N, double *K);
+hipError_t shk_sim_text_len(hipStream_t st, const double *K, int N, const int64_t *names_off, const uint8_t *nan_mask, int64_t *row_len, unsigned *bad);
+hipError_t shk_sim_format(hipStream_t st, const double *K, int N, const char *names, const int64_t *names_off, const uint8_t *nan_mask,
+                          const int64_t *row_off, uint8_t *out);
 hipError_t shk_repack_bits(hipStream_t, const uint8_t *, int64_t, int64_t, int64_t, int, int, uint64_t *, uint8_t *);
 hipError_t shk_lmm_linear(hipStream_t, int, const uint64_t *, int64_t, int, int, const double *, const double *,
                           const double *, const double *, const uint64_t *, const uint64_t *, int, const double *, LmmLinOut);
@@ -1169,6 +1172,79 @@ int sh_sim_finish(sh_ctx *c, double *K)
     HIPCHK(shk_sim_finish(c->stream, c->sim_K, c->NS, c->N, c->sim_out));
     HIPCHK(hipMemcpyAsync(K, c->sim_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return SH_OK;
+}
+
+// The matrix as the reference prints it (simtext_kernels.hip): K == NULL formats the accumulated matrix (c->sim_out, as sh_sim_finish makes
+// it), else the caller's N x N matrix after an upload.  The row lengths come back for the scan and the capacity check; the text is made
+// only where it fits.
+namespace {
+struct SimTextBufs {                                   // the call's device memory, freed however it ends
+    double *K = nullptr; char *names = nullptr; int64_t *names_off = nullptr, *row_len = nullptr, *row_off = nullptr; uint8_t *mask = nullptr, *out = nullptr;
+    unsigned *bad = nullptr;
+    ~SimTextBufs() { hipFree(K); hipFree(names); hipFree(names_off); hipFree(row_len); hipFree(row_off); hipFree(mask); hipFree(out); hipFree(bad); }
+};
+}
+
+int sh_sim_text(sh_ctx *c, const double *K, const char *names, const int64_t *names_off, const uint8_t *nan_mask, uint8_t *out, int64_t cap, int64_t *len)
+{
+    if (!c) return fail(SH_EINVAL, "null ctx");
+    if (!names || !names_off || !len) return fail(SH_EINVAL, "sh_sim_text: null argument");
+    if (!K && !c->sim_K) return fail(SH_EINVAL, "sh_sim_begin has not run");
+    const int N = c->N;
+    for (int j = 0; j < N; ++j) {
+        if (names_off[j + 1] < names_off[j]) return fail(SH_EINVAL, "sh_sim_text: names_off must not decrease");
+        for (int64_t k = names_off[j]; k < names_off[j + 1]; ++k)
+            if (names[k] == '\t' || names[k] == '\n' || names[k] == '\r' || names[k] == '"')
+                return fail(SH_EINVAL, "sh_sim_text: name " + std::to_string(j) + " holds a tab, a quote or a line end (the reference's writer would quote it)");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    const size_t n = (size_t)N * N;
+    const int64_t name_bytes = names_off[N] - names_off[0];
+    SimTextBufs b;
+    const double *dK;
+    if (K) {
+        HIPCHK(dmalloc(&b.K, n));
+        HIPCHK(hipMemcpyAsync(b.K, K, sizeof(double) * n, hipMemcpyHostToDevice, st));
+        dK = b.K;
+    } else {
+        if (!c->sim_out) HIPCHK(dmalloc(&c->sim_out, n));
+        HIPCHK(shk_sim_finish(st, c->sim_K, c->NS, N, c->sim_out));
+        dK = c->sim_out;
+    }
+    std::vector<int64_t> off0((size_t)N + 1);               // offsets into the uploaded names, which begin at the first name
+    for (int j = 0; j <= N; ++j) off0[(size_t)j] = names_off[j] - names_off[0];
+    HIPCHK(dmalloc(&b.names, (size_t)std::max<int64_t>(name_bytes, 1)));
+    HIPCHK(dmalloc(&b.names_off, (size_t)N + 1));
+    HIPCHK(dmalloc(&b.row_len, (size_t)N));
+    HIPCHK(dmalloc(&b.row_off, (size_t)N));
+    HIPCHK(dmalloc(&b.bad, 1));
+    if (name_bytes) HIPCHK(hipMemcpyAsync(b.names, names + names_off[0], (size_t)name_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b.names_off, off0.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b.bad, 0, sizeof(unsigned), st));
+    if (nan_mask) {
+        HIPCHK(dmalloc(&b.mask, (size_t)N));
+        HIPCHK(hipMemcpyAsync(b.mask, nan_mask, (size_t)N, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(shk_sim_text_len(st, dK, N, b.names_off, b.mask, b.row_len, b.bad));
+    std::vector<int64_t> row((size_t)N);
+    unsigned bad = 0;
+    HIPCHK(hipMemcpyAsync(row.data(), b.row_len, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bad, b.bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad & 1u) return fail(SH_EINVAL, "sh_sim_text: the matrix holds a non-integer (or a NaN outside nan_mask): not a count");
+    if (bad & 2u) return fail(SH_EINVAL, "sh_sim_text: the matrix holds a negative value: not a count");
+    if (bad & 4u) return fail(SH_EINVAL, "sh_sim_text: the matrix holds a value of 1e15 or more: too large for the integer notation");
+    int64_t total = name_bytes + N + 1;                     // the header: a tab before every name, the line end
+    for (int i = 0; i < N; ++i) { const int64_t l = row[(size_t)i]; row[(size_t)i] = total; total += l; }
+    *len = total;
+    if (!out || cap < total) return SH_OK;                  // (the length query: nothing is written)
+    HIPCHK(hipMemcpyAsync(b.row_off, row.data(), sizeof(int64_t) * (size_t)N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMalloc((void **)&b.out, (size_t)total + 16));
+    HIPCHK(shk_sim_format(st, dK, N, b.names, b.names_off, b.mask, b.row_off, b.out));
+    HIPCHK(hipMemcpyAsync(out, b.out, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return SH_OK;
 }
 

@@ -18,7 +18,7 @@ struct sh_select {
     hipStream_t stream = nullptr;
     int32_t *d_map = nullptr;
     struct Slot { uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr; int32_t *h_counts = nullptr, *d_counts = nullptr;
-                  int64_t cap_in = 0, cap_rows = 0; hipEvent_t done = nullptr; } slot[2];
+                  int64_t cap_in = 0, cap_rows = 0, cap_rows_dev = 0; hipEvent_t done = nullptr, used = nullptr; } slot[2];
 };
 
 // every entry in [0, n_src), no entry twice
@@ -54,6 +54,7 @@ void sh_select_close(sh_select *s)
         if (sl.h_counts) hipHostFree(sl.h_counts);
         hipFree(sl.d_in); hipFree(sl.d_out); hipFree(sl.d_counts);
         if (sl.done) hipEventDestroy(sl.done);
+        if (sl.used) hipEventDestroy(sl.used);
     }
     hipFree(s->d_map);
     if (s->stream) hipStreamDestroy(s->stream);
@@ -64,7 +65,7 @@ static int select_open_device(sh_select *s, const int32_t *map)
 {
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    for (auto &sl : s->slot) HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    for (auto &sl : s->slot) { HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&sl.used, hipEventDisableTiming)); }
     HIPCHK(dmalloc(&s->d_map, (size_t)s->n_dst));
     HIPCHK(hipMemcpyAsync(s->d_map, map, (size_t)s->n_dst * 4, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));                // (the caller's table is pageable and its own again from here on)
@@ -86,7 +87,8 @@ sh_select *sh_select_open(sh_ctx *ctx, int n_src, const int32_t *map, int n_dst)
     return s;
 }
 
-static int select_ensure(sh_select *s, sh_select::Slot &sl, int64_t rows, int64_t in_bytes, bool stage_in)
+// stage_out: the rows and counts come back to the host (pinned h_out, h_counts); without it the slot's outputs stay on the device
+static int select_ensure(sh_select *s, sh_select::Slot &sl, int64_t rows, int64_t in_bytes, bool stage_in, bool stage_out = true)
 {
     const int64_t out_rb = (((int64_t)s->n_dst + 63) / 64) * 8;
     if (in_bytes > sl.cap_in) {
@@ -97,17 +99,22 @@ static int select_ensure(sh_select *s, sh_select::Slot &sl, int64_t rows, int64_
         sl.cap_in = in_bytes;
     }
     if (stage_in && !sl.h_in) HIPCHK(hipHostMalloc((void **)&sl.h_in, (size_t)sl.cap_in, hipHostMallocDefault));
-    if (rows > sl.cap_rows) {
+    if (stage_out && rows > sl.cap_rows) {
         HIPCHK(hipStreamSynchronize(s->stream));
         if (sl.h_out) hipHostFree(sl.h_out);
         if (sl.h_counts) hipHostFree(sl.h_counts);
-        hipFree(sl.d_out); hipFree(sl.d_counts);
-        sl.h_out = sl.d_out = nullptr; sl.h_counts = sl.d_counts = nullptr; sl.cap_rows = 0;
+        sl.h_out = nullptr; sl.h_counts = nullptr; sl.cap_rows = 0;
         HIPCHK(hipHostMalloc((void **)&sl.h_out, (size_t)(rows * out_rb), hipHostMallocDefault));
         HIPCHK(hipHostMalloc((void **)&sl.h_counts, (size_t)rows * 4, hipHostMallocDefault));
+        sl.cap_rows = rows;
+    }
+    if (rows > sl.cap_rows_dev) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        hipFree(sl.d_out); hipFree(sl.d_counts);
+        sl.d_out = nullptr; sl.d_counts = nullptr; sl.cap_rows_dev = 0;
         HIPCHK(hipMalloc((void **)&sl.d_out, (size_t)(rows * out_rb)));
         HIPCHK(dmalloc(&sl.d_counts, (size_t)rows));
-        sl.cap_rows = rows;
+        sl.cap_rows_dev = rows;
     }
     return SH_OK;
 }
@@ -166,6 +173,42 @@ int sh_select_rows_dev(sh_select *s, const void *d_bits, int64_t src_row_bytes, 
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(shk_rows_select(s->stream, d_bits, src_row_bytes, V, s->d_map, s->n_dst, d_out, d_counts));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return SH_OK;
+}
+
+// Host rows of the cache's width into the context's similarity accumulator: every row goes up once and nothing comes back.  Chunks of about
+// 128 MB alternate between the two slots: chunk c is copied into the slot's pinned memory, uploaded and selected on the selector's stream
+// (event `done`); the context's stream waits for that event, accumulates the selected rows (sh_sim_accumulate_dev) and records `used`, which
+// the selector's stream waits for before it writes the slot's rows again -- so chunk c + 1 is staged, uploaded and selected under chunk c's
+// accumulation.  The chunks are large because every accumulation adds whole tiles of K (sim_kernels.hip k_sim_pairs).
+#define SIM_SELECT_CHUNK_BYTES ((int64_t)128 << 20)
+
+int sh_sim_accumulate_select(sh_ctx *c, sh_select *s, const uint8_t *bits, int64_t src_row_bytes, int64_t V)
+{
+    if (!s) return fail(SH_EINVAL, "sh_sim_accumulate_select: null selector");
+    if (!c || c != s->ctx) return fail(SH_EINVAL, "sh_sim_accumulate_select: the selector belongs to another context");
+    if (!c->sim_K) return fail(SH_EINVAL, "sh_sim_begin has not run");
+    const int rc0 = select_check_rows(s->n_src, src_row_bytes, V, bits, bits, bits, "sh_sim_accumulate_select"); if (rc0) return rc0;
+    if (src_row_bytes > shk_rows_select_max_row_bytes()) return fail(SH_ESHAPE, "sh_sim_accumulate_select: the source row is too wide for k_rows_select's row in LDS");
+    if (V == 0) return SH_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const int64_t out_rb = (((int64_t)s->n_dst + 63) / 64) * 8;
+    const int64_t chunk = std::max<int64_t>(1, SIM_SELECT_CHUNK_BYTES / src_row_bytes), n_chunks = (V + chunk - 1) / chunk;
+    for (int64_t ci = 0; ci < n_chunks; ++ci) {
+        sh_select::Slot &sl = s->slot[ci & 1];
+        const int64_t v0 = ci * chunk, nv = std::min(chunk, V - v0);
+        if (ci >= 2) HIPCHK(hipEventSynchronize(sl.done));                 // (the slot's pinned rows have gone up)
+        int rc = select_ensure(s, sl, std::min(chunk, V), std::min(chunk, V) * src_row_bytes, true, false); if (rc) return rc;
+        select_copy(sl.h_in, bits + v0 * src_row_bytes, nv * src_row_bytes);
+        if (ci >= 2) HIPCHK(hipStreamWaitEvent(s->stream, sl.used, 0));    // (the slot's selected rows have been accumulated)
+        HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, (size_t)(nv * src_row_bytes), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(shk_rows_select(s->stream, sl.d_in, src_row_bytes, nv, s->d_map, s->n_dst, sl.d_out, sl.d_counts));
+        HIPCHK(hipEventRecord(sl.done, s->stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, sl.done, 0));
+        rc = sh_sim_accumulate_dev(c, sl.d_out, out_rb, nv); if (rc) return rc;
+        HIPCHK(hipEventRecord(sl.used, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));                               // (which has waited for every chunk's selection)
     return SH_OK;
 }
 

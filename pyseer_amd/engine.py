@@ -243,6 +243,35 @@ class Engine(object):
         _abi.check(self._lib.sh_sim_finish(self._h, K.ctypes.data_as(_abi.c_dp)))
         return K
 
+    def sim_text(self, names, nan_mask=None, K=None):
+        """The matrix as the bytes pd.DataFrame(K, index=names, columns=names).to_csv(sep='\\t') writes, made on the device (sh_sim_text,
+        k_sim_format) -> numpy uint8 array.  K None: the accumulated matrix (sim_begin / sim_accumulate); else a host (n, n) matrix.
+        nan_mask: n flags; the rows and columns of flagged samples are empty fields.  Raises SeerHipError (SH_EINVAL, the case named) for a
+        matrix the integer notation cannot express."""
+        enc = [str(s).encode() for s in names]
+        if len(enc) != self.n:
+            raise AssertionError("%d names for %d samples" % (len(enc), self.n))
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum([len(e) for e in enc], out=off[1:])
+        blob = b"".join(enc)
+        Kp = None
+        if K is not None:
+            K = np.ascontiguousarray(K, dtype=np.float64)
+            if K.shape != (self.n, self.n):
+                raise AssertionError("matrix of shape %s for %d samples" % (K.shape, self.n))
+            Kp = _dp(K)
+        mp = None
+        if nan_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(nan_mask, dtype=bool).reshape(self.n), dtype=np.uint8)
+            mp = mask.ctypes.data_as(_abi.c_u8p)
+        offp = off.ctypes.data_as(C.POINTER(C.c_int64))
+        ln = C.c_int64()
+        _abi.check(self._lib.sh_sim_text(self._h, Kp, blob, offp, mp, None, 0, C.byref(ln)))         # the length query
+        out = np.empty(ln.value, dtype=np.uint8)
+        _abi.check(self._lib.sh_sim_text(self._h, Kp, blob, offp, mp, out.ctypes.data_as(_abi.c_u8p), out.shape[0], C.byref(ln)))
+        assert ln.value == out.shape[0]
+        return out
+
     def glm_info(self):
         a = C.c_int64(); b = C.c_int64()
         _abi.check(self._lib.sh_glm_info(self._h, C.byref(a), C.byref(b)))
@@ -490,6 +519,13 @@ class RowSelector(object):
         torch.cuda.current_stream(bits_t.device).synchronize()       # (the selector's stream is its own: the rows must be there)
         _abi.check(self._lib.sh_select_rows_dev(self._h, C.c_void_p(bits_t.data_ptr()), rb, V, C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr())))
         return out, counts
+
+    def sim_accumulate(self, bits):
+        """bits (V, src_row_bytes) uint8 host rows into the engine's similarity accumulator (after sim_begin): uploaded once, selected and
+        accumulated on the device (sh_sim_accumulate_select); complete at return."""
+        bits = _select_rows_in(bits, self.n_src)
+        if bits.shape[0]:
+            _abi.check(self._lib.sh_sim_accumulate_select(self._eng._h, self._h, bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], bits.shape[0]))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1765,6 +1765,73 @@ def check_packed_cache(p, path, select=None):
     return sample_map
 
 
+def _map_packed_cache(path):
+    """The cache memory-mapped and its header read -> (mapping, its size, stored sample names, stored row width, offset of the first block).
+    A block's bit rows are a VIEW into the mapping (round 3: f.read() of a 170 MB block was a 40 ms copy per block, more than the GPU needs
+    to test it): the engine's host-to-device copy reads the page cache directly."""
+    import mmap
+    with open(path, "rb") as f:
+        size = os.fstat(f.fileno()).st_size
+        if size < 24:
+            raise IOError("%s is not a packed k-mer cache" % path)
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    try:
+        mm.madvise(mmap.MADV_SEQUENTIAL)
+    except (AttributeError, OSError):
+        pass
+    if mm[:8] != _PK_MAGIC:
+        raise IOError("%s is not a packed k-mer cache" % path)
+    ns, rb = np.frombuffer(mm, dtype="<u4", count=2, offset=8)
+    (ln,) = np.frombuffer(mm, dtype="<u8", count=1, offset=16)
+    pos = 24 + int(ln)
+    if pos > size:
+        raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
+    return mm, size, mm[24:pos].decode().split("\n"), int(rb), pos
+
+
+def _packed_block_extents(mm, pos, size, rb, path):
+    """The index pass over a mapped cache from its first block at `pos`: the 16-byte header of every stored block, up to the terminator (a few
+    hundred bytes of the mapping are touched) -> (rows of every stored block, (offset, bytes) of its bit rows, (offset, name bytes) of what
+    precedes them: name offsets, counts, names).  A cache that ends before its terminator raises the IOError every truncated cache meets."""
+    nvs, extents, metas = [], [], []
+    while True:
+        if pos + 16 > size:
+            raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
+        nv, nb = (int(x) for x in np.frombuffer(mm, dtype="<u8", count=2, offset=pos))
+        pos += 16
+        if nv == 0:
+            return nvs, extents, metas
+        metas.append((pos, nb))
+        pos += 8 * (nv + 1) + 4 * nv + nb
+        if pos + nv * rb > size:
+            raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
+        extents.append((pos, nv * rb))
+        nvs.append(nv)
+        pos += nv * rb
+
+
+def open_packed_cache_rows(path):
+    """A packed cache's stored rows as they lie in the file, for a consumer that restricts them to its samples itself (similarity
+    --load-packed: RowSelector.sim_accumulate) -> (stored sample names, stored row width, total rows, rows): rows() yields per stored block
+    its (nv, row width) uint8 rows, a view of the mapping, and (row, name) of its lines that no stored sample carries.  Every block header is
+    walked here, before a row is read: a cache that is not one, or is truncated, raises IOError now."""
+    mm, size, stored, rb, pos = _map_packed_cache(path)
+    if rb != row_bytes_for(len(stored)):
+        raise IOError("packed cache row width mismatch")
+    nvs, extents, metas = _packed_block_extents(mm, pos, size, rb, path)
+
+    def rows():
+        for nv, (at, nbytes), (meta, nb) in zip(nvs, extents, metas):
+            counts = np.frombuffer(mm, dtype="<i4", count=nv, offset=meta + 8 * (nv + 1))
+            empty = []
+            if not counts.all():
+                off = np.frombuffer(mm, dtype="<i8", count=nv + 1, offset=meta)
+                names = meta + 8 * (nv + 1) + 4 * nv
+                empty = [(int(i), mm[names + int(off[i]):names + int(off[i + 1])].decode()) for i in np.nonzero(counts == 0)[0]]
+            yield np.frombuffer(mm, dtype=np.uint8, count=nbytes, offset=at).reshape(nv, rb), empty
+    return stored, rb, sum(nvs), rows
+
+
 def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns=False, want_samples=False, part=None, raw=False, device=None, ahead=2,
                               say_empty=True, select=None):
     """PackedBlock stream from a packed cache written by --save-packed; the samples (and their order) must be the run's own.
@@ -1784,30 +1851,10 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
     n = len(samples)
 
     def raw_blocks():
-        # The cache is memory-mapped and a block's bit rows are a VIEW into the mapping (round 3: f.read() of a 170 MB block was a 40 ms copy
-        # per block, more than the GPU needs to test it): the engine's host-to-device copy reads the page cache directly.
-        import mmap
-        with open(path, "rb") as f:
-            size = os.fstat(f.fileno()).st_size
-            if size < 24:
-                raise IOError("%s is not a packed k-mer cache" % path)
-            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-        try:
-            mm.madvise(mmap.MADV_SEQUENTIAL)
-        except (AttributeError, OSError):
-            pass
-        if mm[:8] != _PK_MAGIC:
-            raise IOError("%s is not a packed k-mer cache" % path)
-        ns, rb = np.frombuffer(mm, dtype="<u4", count=2, offset=8)
-        (ln,) = np.frombuffer(mm, dtype="<u8", count=1, offset=16)
-        pos = 24 + int(ln)
-        if pos > size:
-            raise IOError("truncated packed cache %s (delete it, or run without --load-packed)" % path)
-        stored = mm[24:pos].decode().split("\n")
+        mm, size, stored, rb, pos = _map_packed_cache(path)
         sample_map = _cache_sample_map(stored, samples, select)
-        if int(rb) != row_bytes_for(len(stored)):
+        if rb != row_bytes_for(len(stored)):
             raise IOError("packed cache row width mismatch")
-        rb = int(rb)
         select_rows, select_close = (None, None) if sample_map is None else _open_selector(select, len(stored), sample_map)
         use_dma = want_dma and sample_map is None
         windows = _DmaWindows(device) if use_dma else None
@@ -1827,17 +1874,7 @@ def iter_packed_blocks_cached(p, path, min_af, max_af, block_size, want_patterns
             # stored blocks until it holds block_size rows (merged() below); a part owns whole such groups -- the groups whose first row falls
             # into its share of the rows -- so every part hands the engine exactly the blocks the single stream would, and output that depends
             # on where blocks end (fit_lmm's filtered-first order, its stale-k lineage: pyseer/lmm.py:160-217) does not change
-            start = pos
-            nvs, extents = [], []
-            while True:
-                at = need(16)
-                nv, nb = (int(x) for x in np.frombuffer(mm, dtype="<u8", count=2, offset=at))
-                if nv == 0:
-                    break
-                need(8 * (nv + 1) + 4 * nv + nb)
-                extents.append((need(nv * rb), nv * rb))
-                nvs.append(nv)
-            pos = start
+            nvs, extents, _ = _packed_block_extents(mm, pos, size, rb, path)
         if part is not None:
             total = sum(nvs)
             i_, n_ = part
