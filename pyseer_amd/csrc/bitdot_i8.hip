@@ -3,7 +3,7 @@
 // For every variant v and column c < NE:   out[c][v] = sum over the carriers i of v of vals[i][c]
 // (vals = (w0_i, w0_i z_i0 .. w0_i z_i,Q-1, r0_i) at the null model; pyseer/model.py:316-344 fits the variant's model from there, and the
 // information matrix of the finishing kernels is a difference FROM these sums -- glm_kernels.hip: k_glm_first_step, k_glm_dpass, k_glm_finish;
-// firth_fast.hip takes the k-row of I from them).  Round 3 did this with nibble tables in LDS on the vector ALU (k_glm_bitdot, 0.5 ms per 2^18
+// firth_fast.hip takes the k-row of I from them).  Round 3 did this with nibble tables in LDS on the vector ALU (a kernel since removed: 0.5 ms per 2^18
 // variants at N = 5000, LDS-bound); here it is a GEMM  bits (V x N, 0/1) x digits (N x 8 NE, int8):
 //   * every column is scaled by a power of two to |x| < 2^62, rounded to an integer and written in EIGHT balanced base-256 digits in
 //     [-128, 127]  (bitdot_i8_digits, host, once per run);  v_mfma_i32_32x32x32_i8 accumulates bit x digit exactly in int32

@@ -25,7 +25,6 @@
 // operand (32 monomials x 16 samples) is read from the run's table (GlmParams.ff_tab) one 16-byte fragment per lane.  Accumulators: T2 tiles
 // (w . m2), T3 tiles (c . m3), T2 tiles (c k . m2), 16 registers each: 240 AGPRs at Q = 10; one wavefront per SIMD.
 #include "firth_fast_common.h"
-#ifndef FF_F32_TU
 extern "C" int shk_firth_fast_supported(int Q) { return Q >= 1 && Q <= 10; }
 extern "C" int shk_firth_fast_row2(int Q, int a, int b) { return ff_row2(a, b, Q + 1); }
 extern "C" int shk_firth_fast_tiles(int Q, int *t2, int *t3, int *rs)
@@ -34,7 +33,6 @@ extern "C" int shk_firth_fast_tiles(int Q, int *t2, int *t3, int *rs)
     *t2 = (n2 + 31) / 32; *t3 = (n3 + 31) / 32; *rs = (Q + 3 + 1) & ~1;
     return 0;
 }
-#endif
 
 // the 32 rows of one accumulator tile, every lane seeing all of them: register r of a lane holds row (r & 3) + 8 (r >> 2) + 4 h
 __device__ __forceinline__ void ff_rows(const ff_v16f &acc, int h, float (&row)[32])
@@ -118,7 +116,7 @@ __device__ __forceinline__ double ff_xor32(double x) { return __shfl_xor(x, 32);
 //   fw state on entry (as k_firth_eval2): beta = last accepted point, cand = the point to evaluate, fcur = one-pass F at beta, snp = norm of the
 //   step that led to beta, iter = accepted steps so far (-1: cand is the start vector, nothing to compare with).
 //   exact_list: slots for k_firth_eval2 (the finishing evaluation, or a fit that leaves the fast passes)
-template <int Q, bool F32>
+template <int Q>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, FirthWork fw, const int *__restrict__ fast_list,
                   const int *__restrict__ fast_count, int *__restrict__ next_fast, int *__restrict__ next_fast_count,
@@ -141,7 +139,6 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     const int N = P.N;
     const int NG = (N + 15) >> 4;
     // beta (columns as given) -> the standardised basis x_s = (1, k, (z - m) / s):  b_s0 = b0 + sum m_j b_j,  b_s(2+j) = s_j b_(2+j)
-    typedef std::conditional_t<F32, float, double> RT;     // the arithmetic type of the sample loop
     double cand[PC], bs[PC];
 #pragma unroll
     for (int a = 0; a < PC; ++a) cand[a] = fw.st[(int64_t)(fw_cand<PC>() + a) * cap + s];
@@ -162,35 +159,32 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     for (int t = 0; t < NACC; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    RT nU[PC], Ik0 = 0;                                    // -score = sum (mu - y) x;  I11 = sum w k
-    RT bsr[PC];
+    double nU[PC], Ik0 = 0;                                // -score = sum (mu - y) x;  I11 = sum w k
 #pragma unroll
-    for (int a = 0; a < PC; ++a) { nU[a] = 0; bsr[a] = (RT)bs[a]; }
+    for (int a = 0; a < PC; ++a) nU[a] = 0;
     double apos = 0.0, seta = 0.0, prod = 1.0;                              // (apos, seta: twice the sum of max(s eta, 0), as sum |eta| + sum s eta)
     int pexp = 0;
     // The run's tables reach the block through LDS: per 16-sample group the NTA x 2 fragment blocks of the monomial table (1 KB each: one
     // wave-wide LDS-DMA) and the group's 16 sample records (2 KB slot), double buffered; iteration g of the loop below reads records g and
     // the fragments of group g - 1 (the MFMAs trail the samples by one group).
     constexpr int NPIECE = (NTA * 2 + 2 + 3) & ~3, STAGE = NPIECE * 1024;
-    // (the single-precision pass takes the tables' hi halves only: one product per tile, 2^-11 on sums that need 1e-5)
-    constexpr int NFETCH = F32 ? NTA + 2 : NTA * 2 + 2, NPW = (NFETCH + 3) / 4;     // 1 KB pieces, NPW per wavefront (the last ones padding)
+    constexpr int NFETCH = NTA * 2 + 2, NPW = (NFETCH + 3) / 4;                 // 1 KB pieces, NPW per wavefront (the last ones padding)
     // Ring of FOUR stages, copies issued THREE iterations ahead (round 6; was three / two).  Iteration g reads stage g and -- its last pair's
     // read-ahead: the next group's first record and first fragment -- stage g + 1, so stage g + 1 must have landed for EVERY wavefront when g
     // starts: the end of iteration g - 1 waits for this wavefront's share of everything but the copies issued last (stage g + 2) and then takes
     // the barrier.  With copies only two ahead that wait covered stage g, and stage g + 1 was read on the strength of having been in flight for a
-    // whole iteration: 5 400 cycles at Q = 10 in fp64, but ~1 500 in the single-precision pass at Q <= 3 -- less than a loaded memory system's
-    // latency: 5 of 60 repeated calls differed (tools/gpu_firth_determinism.py, profiles/r06/firth_determinism.txt).
+    // whole iteration: 5 400 cycles at Q = 10 in fp64, but ~1 500 in the single-precision instantiation this kernel then had, at Q <= 3 -- less
+    // than a loaded memory system's latency: 5 of 60 repeated calls differed (tools/gpu_firth_determinism.py, profiles/r06/firth_determinism.txt).
     constexpr int NRING = 4;
     char *const lds = (char *)xw_lds;
     const char *const tab_g = (const char *)P.ff_tab;
-    const char *const rec_g = F32 ? (const char *)P.ff_rec32 : (const char *)P.ff_rec;
+    const char *const rec_g = (const char *)P.ff_rec;
     auto dma = [&](int gi) {                                                    // everything iteration gi reads, into buffer gi % NRING
         char *const buf = lds + (gi % NRING) * STAGE;
         const int gt = max(gi - 1, 0), gr = min(gi, NG - 1);
 #pragma unroll
         for (int q2 = 0; q2 < NPW; ++q2) {
-            const int pf = q2 * 4 + wave;                                       // the pf-th piece fetched = piece pc of the stage
-            const int pc = !F32 ? pf : pf < NTA ? 2 * pf : NTA + pf;
+            const int pc = q2 * 4 + wave;                                       // piece pc of the stage
             const char *src = pc < NTA * 2 ? tab_g + ((int64_t)gt * NTA * 2 + pc) * 1024 : rec_g + (int64_t)gr * (16 * RS * 8) + (pc - NTA * 2) * 1024;
             // (inline assembly, not __builtin_amdgcn_global_load_lds: the compiler cannot tell which LDS bytes a DMA in flight will write, so with
             // the builtin it puts s_waitcnt vmcnt(0) in front of the next LDS read -- the whole latency of the copy just issued, every
@@ -216,44 +210,17 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
             const ff_v4u bh = {B[0][0], B[0][1], B[0][2], B[0][3]}, bl = {B[1][0], B[1][1], B[1][2], B[1][3]};
             const ff_v8h Bh = __builtin_bit_cast(ff_v8h, bh), Bl = __builtin_bit_cast(ff_v8h, bl);
             a = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, a, 0, 0, 0);
-            if constexpr (!F32) {
-                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, a, 0, 0, 0);
-            }
+            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, a, 0, 0, 0);
         };
-        if (FF_ABL & 1) { acc[ta < T2 ? ta : T2 + (ta - T2)][0] += __builtin_bit_cast(float, ah[0] ^ al[1]); return; }
         if (ta < T2) { three(acc[ta], Pw); three(acc[T2 + T3 + ta], Pk); if (ta == 0) three(acc[C::AWK], Px); }
         else three(acc[T2 + (ta - T2)], Pc);
     };
     // one sample: returns the scaled weights (w - w0, c) as floats.  (c k and (w - w0) k are not formed per sample: k is 0 / 1, so their
     // halves are the halves of c and w - w0 under the pair's presence bits -- pair_mask below; round 5: 14 -> 7 instructions per pair)
     // (tail: the group may hold slots behind sample N -- only the last group does; everywhere else the masks `lv` are dropped.  Round 5)
-    auto sample = [&](const RT (&rc)[RS], uint32_t bit, float &wf, float &cf, auto tail) {
+    auto sample = [&](const double (&rc)[RS], uint32_t bit, float &wf, float &cf, auto tail) {
         constexpr bool TAIL = decltype(tail)::value;
-        if constexpr (F32) {
-            // the FIRST pass (at the start vector, some 1e-2 from the fit) in single precision: its step need not be better than the 1e-5 the
-            // next point is from the fit anyway; no log-likelihood (nothing to compare F with yet)
-            const float xd = (float)bit;
-            float eta = fmaf(bsr[1], xd, bsr[0]);
-#pragma unroll
-            for (int j = 0; j < Q; ++j) eta = fmaf(bsr[2 + j], rc[j], eta);
-            const float lv = rc[Q + 1];
-            float t = __builtin_amdgcn_exp2f(fabsf(eta) * -1.4426950408889634f);
-            if (TAIL) t *= lv;
-            const float u = 1.0f + t;
-            float inv = __builtin_amdgcn_rcpf(u);
-            inv = fmaf(fmaf(-u, inv, 1.0f), inv, inv);
-            const float wgt = (t * inv) * inv;
-            const float hm = copysignf(fmaf(-0.5f, t, 0.5f) * inv, eta);
-            float r = fmaf(0.5f, rc[Q], hm);
-            if (TAIL) r *= lv;
-            nU[0] += r; nU[1] = fmaf(xd, r, nU[1]);
-            Ik0 = fmaf(wgt, xd, Ik0);
-#pragma unroll
-            for (int j = 0; j < Q; ++j) nU[2 + j] = fmaf(rc[j], r, nU[2 + j]);
-            wf = fmaf(wgt, (float)FF_SCALE, rc[Q + 2]);                          // (the record holds -2^12 w0)
-            cf = -(wgt * hm) * (float)FF_SCALE;
-        } else {
         const double xd = (double)bit;
         double eta = fma(bs[1], xd, bs[0]);
 #pragma unroll
@@ -280,7 +247,6 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
         for (int j = 0; j < Q; ++j) nU[2 + j] = fma(rc[j], r, nU[2 + j]);
         wf = (float)fma(wgt, FF_SCALE, rc[Q + 2]);                              // 2^12 (w - w0) (the record holds -2^12 w0: one rounding either way): I = I(null model) + sum (w - w0) m2, the sum an order of magnitude smaller than I
         cf = (float)(-(wgt * hm) * FF_SCALE);                                   // c = w (1/2 - mu)
-        }
     };
     // 0xffff in the half of the even / the odd sample of pair pp that carries the variant (bits 2 pp, 2 pp + 1 of the group's byte)
     auto pair_mask = [&](uint32_t byte, int pp) -> uint32_t {
@@ -289,22 +255,15 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     };
     auto stash = [&](uint32_t (&B)[2][4], int e, float a, float b) {
         const ff_v2h hh = __builtin_convertvector(ff_v2f{a, b}, ff_v2h);
-        if constexpr (F32) { B[0][e] = __builtin_bit_cast(uint32_t, hh); B[1][e] = 0u; return; }
         const ff_v2f back = __builtin_convertvector(hh, ff_v2f);
         const ff_v2h ll = __builtin_convertvector(ff_v2f{a - back.x, b - back.y}, ff_v2h);
         B[0][e] = __builtin_bit_cast(uint32_t, hh); B[1][e] = __builtin_bit_cast(uint32_t, ll);
     };
     // sample j (0..7) of this lane's half of the group in buffer `buf`
-    auto fetch_rec = [&](const char *buf, int j, RT (&rc)[RS]) {
-        if constexpr (F32) {                                                    // (single-precision records: the same slots, half filled)
-            const ff_v2f *r = (const ff_v2f *)(buf + NTA * 2048 + (8 * h + j) * (RS * 8));
+    auto fetch_rec = [&](const char *buf, int j, double (&rc)[RS]) {
+        const ff_v2d *r = (const ff_v2d *)(buf + NTA * 2048 + (8 * h + j) * (RS * 8));
 #pragma unroll
-            for (int k2 = 0; k2 < RS / 2; ++k2) { const ff_v2f x = r[k2]; rc[2 * k2] = x.x; rc[2 * k2 + 1] = x.y; }
-        } else {
-            const ff_v2d *r = (const ff_v2d *)(buf + NTA * 2048 + (8 * h + j) * (RS * 8));
-#pragma unroll
-            for (int k2 = 0; k2 < RS / 2; ++k2) { const ff_v2d x = r[k2]; rc[2 * k2] = x.x; rc[2 * k2 + 1] = x.y; }
-        }
+        for (int k2 = 0; k2 < RS / 2; ++k2) { const ff_v2d x = r[k2]; rc[2 * k2] = x.x; rc[2 * k2 + 1] = x.y; }
     };
     // A group = 8 samples per lane = four pairs; the MFMAs of the PREVIOUS group's operands are issued AMONG the pairs' arithmetic (the matrix
     // core works beside the vector ALU only if the instruction stream alternates: sched_group_barrier), table tiles pp, pp + 4, pp + 8 ...
@@ -312,7 +271,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     // the pair.  The tables of iterations g + 2 and g + 3 are in flight while g computes (ring of NRING buffers): the end of an iteration waits for its
     // wavefront's share of g + 1 and g + 2 only.
     constexpr int PER = (NTA + 3) / 4;
-    RT ra[RS], rb[RS];
+    double ra[RS], rb[RS];
     uint64_t w64 = 0, wnext = T[v];
     // fragments of the slot's tiles q2 = lo..hi-1 (tile q2 * 4 + pp)
     auto slot_load = [&](const char *buf, int pp, int lo, int hi, ff_v4u (&ah)[PER], ff_v4u (&al)[PER]) {
@@ -321,7 +280,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
             const int ta = q2 * 4 + pp;
             if (q2 >= lo && q2 < hi && ta < NTA) {
                 ah[q2] = *(const ff_v4u *)(buf + (ta * 2 + 0) * 1024 + lane * 16);
-                if constexpr (!F32) al[q2] = *(const ff_v4u *)(buf + (ta * 2 + 1) * 1024 + lane * 16);   // (the single-precision pass never reads al)
+                al[q2] = *(const ff_v4u *)(buf + (ta * 2 + 1) * 1024 + lane * 16);
             }
         }
     };
@@ -329,7 +288,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
 #pragma unroll
         for (int q2 = 0; q2 < PER; ++q2) {
             const int ta = q2 * 4 + pp;
-            if (q2 >= lo && q2 < hi && ta < NTA) tile_mfma(ta, ah[q2], F32 ? ah[q2] : al[q2]);
+            if (q2 >= lo && q2 < hi && ta < NTA) tile_mfma(ta, ah[q2], al[q2]);
         }
     };
     dma(0);
@@ -346,7 +305,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
             wnext = T[(int64_t)min((g >> 2) + 1, P.NB64 - 1) * Vpad + v];
         }
         const uint32_t byte = ((uint32_t)(w64 >> (16 * (g & 3) + 8 * h)) & 0xffu) ^ flipm;
-        if (!(FF_ABL & 2)) dma(min(g + 3, NG));
+        dma(min(g + 3, NG));
 #if FF_STAGGER
         // the four wavefronts leave the barrier together and would hit the LDS with their reads at the same moments of every pair: a quarter of
         // a pair's time apart they find it free
@@ -366,8 +325,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
             fetch_rec(buf, 2 * pp + 1, rb);
             slot_load(buf, pp, 1, PER, ah, al);
             __builtin_amdgcn_sched_barrier(0);
-            if (FF_ABL & 4) { w0 = (float)ra[0]; c0 = (float)ra[1]; nU[pp] += ra[3]; }
-            else sample(ra, (byte >> (2 * pp)) & 1u, w0, c0, tail);
+            sample(ra, (byte >> (2 * pp)) & 1u, w0, c0, tail);
             slot_mfma(pp, 0, 1, ah, al);
 #if FF_SCHED
 #pragma unroll
@@ -378,16 +336,14 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
 #endif
             // (the fences order instructions with side effects; plain arithmetic is placed wherever its operands allow.  Empty volatile asms that
             // "define" the even sample's results pin its arithmetic in front of the next fence, i.e. UNDER the LDS reads issued above)
-            if constexpr (F32) asm volatile("" : "+v"(w0), "+v"(c0), "+v"(Ik0));
-            else asm volatile("" : "+v"(w0), "+v"(c0), "+v"(apos), "+v"(seta), "+v"(prod), "+v"(Ik0));
+            asm volatile("" : "+v"(w0), "+v"(c0), "+v"(apos), "+v"(seta), "+v"(prod), "+v"(Ik0));
 #pragma unroll
             for (int a = 0; a < PC; ++a) asm volatile("" : "+v"(nU[a]));
             __builtin_amdgcn_sched_barrier(0);
             if (pp < 3) { fetch_rec(buf, 2 * pp + 2, ra); slot_load(buf, pp + 1, 0, 1, ah, al); }
             else { fetch_rec(bufn, 0, ra); slot_load(bufn, 0, 0, 1, ah, al); }
             __builtin_amdgcn_sched_barrier(0);
-            if (FF_ABL & 4) { w1 = (float)rb[0]; c1 = (float)rb[1]; nU[pp] += rb[3]; }
-            else sample(rb, (byte >> (2 * pp + 1)) & 1u, w1, c1, tail);
+            sample(rb, (byte >> (2 * pp + 1)) & 1u, w1, c1, tail);
             stash(Bw, pp, w0, w1); stash(Bc, pp, c0, c1);
             {
                 const uint32_t pm = pair_mask(byte, pp);
@@ -409,10 +365,10 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
         for (int q2 = 0; q2 < 2; ++q2)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { Pw[q2][e] = Bw[q2][e]; Pc[q2][e] = Bc[q2][e]; Pk[q2][e] = Bk[q2][e]; Px[q2][e] = Bx[q2][e]; }
-        if (!F32 && (g & 3) == 3) { int e2; prod = frexp(prod, &e2); pexp += e2; }
+        if ((g & 3) == 3) { int e2; prod = frexp(prod, &e2); pexp += e2; }
         // this wavefront's share of the next TWO iterations' tables has landed (the copies issued last, stage g + 3, may still be in flight), then the bare barrier:
         // everyone's has, and everyone is done reading this iteration's buffer.  (__syncthreads() would add a vmcnt(0) and wait for both)
-        if (!(FF_ABL & 2)) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NPW) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NPW) : "memory");
     };
 #pragma unroll 1
     for (int g = 0; g < NG - 1; ++g) group(g, std::false_type{});
@@ -430,10 +386,10 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     // ---- the two halves' partial sums ----------------------------------------------------------------------------------------------------
     double nUd[PC], Ik0d;
 #pragma unroll
-    for (int a = 0; a < PC; ++a) { const double x = (double)nU[a]; nUd[a] = x + ff_xor32(x); }
-    { const double x = (double)Ik0; Ik0d = x + ff_xor32(x); }
-    double ll = 0.0;                                                        // (the single-precision pass has no likelihood: nothing to compare it with)
-    if constexpr (!F32) {
+    for (int a = 0; a < PC; ++a) nUd[a] = nU[a] + ff_xor32(nU[a]);
+    Ik0d = Ik0 + ff_xor32(Ik0);
+    double ll;
+    {
         int e2; prod = frexp(prod, &e2); pexp += e2;
         double lp = fma((double)pexp, 0.6931471805599453, log(prod));
         apos = 0.5 * (apos + seta);
@@ -448,7 +404,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     double rho = 0.0;
     ff_all2i<Q>(acc, h, unscale, P.ff_inull, I, rho, std::make_integer_sequence<int, T2>{});
     I[sidx(1, 0)] = Ik0d; I[sidx(1, 1)] = Ik0d;
-    {   // the k-row: sum w k z_j = (the null model's part: the carrier sums of w0 z_j, k_glm_bitdot; of the complement: the totals minus them)
+    {   // the k-row: sum w k z_j = (the null model's part: the carrier sums of w0 z_j, shk_bitdot_i8; of the complement: the totals minus them)
         // + the matrix-core sum of (w - w0) k z_j = rows 1..Q of the degree-2 table's tile 0
         float row[32];
         ff_rows(acc[C::AWK], h, row);
@@ -538,7 +494,7 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
     // log-likelihood, I = I(null) + the matrix-core sum of (w - w0) m2 (~1e-7 on log det), in the reference's columns (det I = det I_s prod s_j^2);
     // I11 = sum w k in fp64 (the complement's: I00 - I11').  A last step above 1e-7 keeps the exact evaluation, and so does a fit whose weights
     // have moved far from the null model's (rho > FF_RHO: a strong effect): the matrix-core sum's 1e-6 then shows in log det I at ~1e-6 rho.
-    if (last && fin && dmax <= FF_FIN_TOL && rho <= FF_RHO && !(FF_ABL & 8)) {
+    if (last && fin && dmax <= FF_FIN_TOL && rho <= FF_RHO) {
         double lsd = 0.0;
 #pragma unroll
         for (int j = 0; j < Q; ++j) lsd += log(P.wstd[Q + j]);
@@ -563,57 +519,34 @@ void k_firth_fast(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, Fir
         if (!last) { fw.iter[s] = -1; }
         list_push(true, exact_list, exact_count, s);
     } else {
-        fw.st[(int64_t)fw_fcur<PC>() * cap + s] = F32 ? (double)INFINITY : F;
+        fw.st[(int64_t)fw_fcur<PC>() * cap + s] = F;
         fw.st[(int64_t)fw_snp<PC>() * cap + s] = sn;
         list_push(true, next_fast, next_fast_count, s);
     }
 }
 
-template <int Q, bool F32>
+template <int Q>
 static hipError_t launch_firth_fast(hipStream_t st, int64_t n, const uint64_t *T, int64_t Vpad, GlmParams P, FirthWork fw, const int *in_list,
                                     const int *in_count, int *next_fast, int *next_fast_count, int *exact_list, int *exact_count, int64_t V, double *out,
                                     uint32_t *flags)
 {
     if (n <= 0) return hipSuccess;
     constexpr size_t lds = 4 * (size_t)((FFC<Q>::NTA * 2 + 2 + 3) & ~3) * 1024;      // NRING stages
-    hipLaunchKernelGGL((k_firth_fast<Q, F32>), dim3((unsigned)((n + 127) / 128)), dim3(256), lds, st, T, Vpad, P, fw, in_list, in_count, next_fast, next_fast_count,
+    hipLaunchKernelGGL((k_firth_fast<Q>), dim3((unsigned)((n + 127) / 128)), dim3(256), lds, st, T, Vpad, P, fw, in_list, in_count, next_fast, next_fast_count,
                        exact_list, exact_count, V, out, flags);
     return hipGetLastError();
 }
 
-// Two translation units from this file (the kernel is large, and there are two per Q): firth_fast.o holds the fp64 kernels and the entry points,
-// firth_fast32.o (-DFF_F32_TU) the single-precision first pass.
-#ifdef FF_ONLY_Q
-#define FF_ALL_Q(X) X(FF_ONLY_Q)
-#else
 #define FF_ALL_Q(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#endif
-#define FF_LAUNCH_ARGS hipStream_t st, int Q, int64_t n, const uint64_t *T, int64_t Vpad, GlmParams P, double *fst, int *fiter, int *fhalv, int *fvar, \
-                       int64_t fcap, const int *in_list, const int *in_count, int *next_fast, int *next_fast_count, int *exact_list, int *exact_count, \
-                       int64_t V, double *out, uint32_t *flags
-#ifdef FF_F32_TU
-extern "C" hipError_t shk_firth_fast_launch32(FF_LAUNCH_ARGS)
+extern "C" hipError_t shk_firth_fast_launch(hipStream_t st, int Q, int64_t n, const uint64_t *T, int64_t Vpad, GlmParams P, double *fst, int *fiter, int *fhalv,
+                                            int *fvar, int64_t fcap, const int *in_list, const int *in_count, int *next_fast, int *next_fast_count,
+                                            int *exact_list, int *exact_count, int64_t V, double *out, uint32_t *flags)
 {
     FirthWork fw{fst, fiter, fhalv, fvar, fcap, nullptr, nullptr, nullptr, nullptr};
-#define FF_CASE(q) case q: return launch_firth_fast<q, true>(st, n, T, Vpad, P, fw, in_list, in_count, next_fast, next_fast_count, exact_list, exact_count, V, out, flags);
+#define FF_CASE(q) case q: return launch_firth_fast<q>(st, n, T, Vpad, P, fw, in_list, in_count, next_fast, next_fast_count, exact_list, exact_count, V, out, flags);
     switch (Q) {
         FF_ALL_Q(FF_CASE)
     default: return hipErrorInvalidValue;
     }
 #undef FF_CASE
 }
-#else
-extern "C" hipError_t shk_firth_fast_launch32(FF_LAUNCH_ARGS);
-extern "C" hipError_t shk_firth_fast_launch(FF_LAUNCH_ARGS, int f32)
-{
-    if (f32) return shk_firth_fast_launch32(st, Q, n, T, Vpad, P, fst, fiter, fhalv, fvar, fcap, in_list, in_count, next_fast, next_fast_count, exact_list,
-                                            exact_count, V, out, flags);
-    FirthWork fw{fst, fiter, fhalv, fvar, fcap, nullptr, nullptr, nullptr, nullptr};
-#define FF_CASE(q) case q: return launch_firth_fast<q, false>(st, n, T, Vpad, P, fw, in_list, in_count, next_fast, next_fast_count, exact_list, exact_count, V, out, flags);
-    switch (Q) {
-        FF_ALL_Q(FF_CASE)
-    default: return hipErrorInvalidValue;
-    }
-#undef FF_CASE
-}
-#endif

@@ -19,9 +19,6 @@ typedef double ff_v2d __attribute__((ext_vector_type(2)));
 #ifndef FF_FIN_TOL
 #define FF_FIN_TOL 1e-7            /* a fit whose LAST step (any coordinate) is at most this is finished in the pass that found it (F to second order, I11 as it is) */
 #endif
-#ifndef FF_ABL
-#define FF_ABL 0                   /* timing ablations (results meaningless): 1 = no MFMAs, 2 = no LDS-DMA / barriers, 4 = no sample arithmetic; 8 (results valid) = every fit finished by the exact kernel */
-#endif
 #ifndef FF_RHO
 #define FF_RHO 0.05               /* largest relative change of I's diagonal against the null model for a fit to be finished from the one-pass F */
 #endif

@@ -1,5 +1,5 @@
-// firth_fast_w.hip -- the one-pass Firth iteration's FIRST pass (single precision, firth_fast.hip: k_firth_fast<Q, true>) at TWO wavefronts
-// per SIMD (round 5).
+// firth_fast_w.hip -- the one-pass Firth iteration's FIRST pass (firth_fast.hip's iteration, the sample loop in single precision) at TWO
+// wavefronts per SIMD (round 5).
 //
 // Why.  k_firth_fast holds the whole third-moment tensor of 32 variants in one wavefront's accumulators (256 AGPRs at Q = 10), i.e. ONE
 // wavefront per SIMD -- and one wavefront issues a vector instruction every 5.2-6 cycles whatever its kind (tools/ubench/valu_rate.hip,
@@ -15,14 +15,12 @@
 // not done here redundantly on four lanes: the sums are handed over through a workspace (FFW<Q>::ROWS floats per fit, rows x fits) to
 // k_firth_fastw_fin, one lane per fit, which runs firth_fast.hip's epilogue on them.
 //
-// Same mathematics as k_firth_fast<Q, true> (same start, same sums up to the order of the additions, same routing); the pass exists to put
-// the iterate 1e-5 from the fit, the fp64 passes that follow are firth_fast.hip's (model.py:414-504).
+// Same mathematics as k_firth_fast (same start, same sums, same routing) with the sample loop in single precision and the tables' hi halves
+// only: the first pass runs at the start vector, some 1e-2 from the fit, and its step need not be better than the 1e-5 the next point is
+// from the fit anyway.  The fp64 passes that follow are firth_fast.hip's (model.py:414-504).
 #include "firth_fast_common.h"
 
 typedef float ffw_v4f __attribute__((ext_vector_type(4)));
-#ifndef FFW_ABL
-#define FFW_ABL 0                  /* timing ablations of k_firth_fastw_fin (results meaningless): 1 = no carrier count, 2 = no contraction */
-#endif
 
 #ifndef FFW_RHO2
 #define FFW_RHO2 0.03
@@ -309,7 +307,7 @@ __device__ __forceinline__ void ffw_all2k(const float *__restrict__ ws, int64_t 
     (one(std::integral_constant<int, Ts>{}), ...);
 }
 
-// One lane per fit of fast_list.  State on entry and routing exactly as k_firth_fast<Q, true> (firth_fast.hip): the single-precision pass has no
+// One lane per fit of fast_list.  State on entry and routing as k_firth_fast (firth_fast.hip), except that the single-precision pass has no
 // likelihood (F = the determinant's half only, never compared: fcur = +inf is what the next pass finds).
 template <int Q>
 __global__ __launch_bounds__(64) void k_firth_fastw_fin(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P, FirthWork fw, const int *__restrict__ fast_list,
@@ -331,9 +329,7 @@ __global__ __launch_bounds__(64) void k_firth_fastw_fin(const uint64_t *__restri
 #pragma unroll
     for (int a = 0; a < PC; ++a) cand[a] = fw.st[(int64_t)(fw_cand<PC>() + a) * cap + s];
     int carriers = 0;
-#if !(FFW_ABL & 1)
     for (int sb = 0; sb < P.NB64; ++sb) carriers += __popcll(T[(int64_t)sb * Vpad + v]);
-#endif
     const bool flip = 2 * carriers > N;
     double nUd[PC];
 #pragma unroll
@@ -384,10 +380,8 @@ __global__ __launch_bounds__(64) void k_firth_fastw_fin(const uint64_t *__restri
     double gp[PC];
 #pragma unroll
     for (int a = 0; a < PC; ++a) gp[a] = 0.0;
-#if !(FFW_ABL & 2)
     ffw_all3<Q>(ws, ws_cap, li, unscale, Vm, gp, std::make_integer_sequence<int, T3>{});
     ffw_all2k<Q>(ws, ws_cap, li, unscale, Vm, gp, std::make_integer_sequence<int, T2>{});
-#endif
     double U[PC], d[PC];
 #pragma unroll
     for (int a = 0; a < PC; ++a) U[a] = gp[a] - nUd[a];
@@ -454,7 +448,7 @@ __global__ __launch_bounds__(64) void k_firth_fastw_fin(const uint64_t *__restri
     }
     fw.iter[s] = iter; fw.halv[s] = 0;
     const bool last = iter > 0 && sn < 1e-4;
-    // (the single-precision pass finishes no fit: a candidate that meets the stop rule goes to k_firth_eval2, as in k_firth_fast<Q, true>)
+    // (the single-precision pass finishes no fit: a candidate that meets the stop rule goes to k_firth_eval2)
     if (last || !fin || iter >= FF_MAXIT) {
         fw.st[(int64_t)fw_fcur<PC>() * cap + s] = INFINITY;
         fw.st[(int64_t)fw_snp<PC>() * cap + s] = last ? sn : INFINITY;
@@ -483,11 +477,7 @@ static hipError_t launch_fastw(hipStream_t st, int64_t n, const uint64_t *T, int
     return hipGetLastError();
 }
 
-#ifdef FF_ONLY_Q
-#define FFW_ALL_Q(X) X(FF_ONLY_Q)
-#else
 #define FFW_ALL_Q(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#endif
 extern "C" hipError_t shk_firth_fastw_launch(hipStream_t st, int Q, int64_t n, const uint64_t *T, int64_t Vpad, GlmParams P, double *fst, int *fiter, int *fhalv,
                                              int *fvar, int64_t fcap, const int *in_list, const int *in_count, int *next_fast, int *next_fast_count,
                                              int *exact_list, int *exact_count, const uint16_t *tab16, const float *rec16, float *ws, int64_t ws_cap)

@@ -27,9 +27,6 @@ __device__ __forceinline__ v2f pkfma2(v2f a, v2f b, v2f c) { return __builtin_el
 #ifndef FIRTH_STEP2_AHEAD
 #define FIRTH_STEP2_AHEAD 1          /* the pairs' covariates fetched one pair ahead (A/B: 6.35 -> 5.86 ms per 259 k variants); 0 = at the top of the pair */
 #endif
-#ifndef FIRTH_STEP2_ABL
-#define FIRTH_STEP2_ABL 0          /* timing ablations of k_firth_step2 (results meaningless): 1 = no hat diagonal, 2 = no LDS reads, 3 = no exp */
-#endif
 #ifndef FIRTH_HAT32_PIVOT
 #define FIRTH_HAT32_PIVOT 1e-2     /* smallest pivot of the standardised factor, relative to its own diagonal entry, for the single-precision hat diagonal */
 #endif
@@ -37,7 +34,7 @@ __device__ __forceinline__ v2f pkfma2(v2f a, v2f b, v2f c) { return __builtin_el
 // ---- start of the rounds (force_firth at large N, GlmParams.firth_warm): the null-model fit plus ONE Newton step of the ordinary likelihood -------
 // fit_firth's fixed point does not depend on where the iteration starts, and at N >= 4096 neither does where it stops, to 1e-7 (sh_glm_setup).
 // Round 2 started at the null-model fit [b0, 0, bz]; there eta is the null model's, so the score and the variant's row of X^T W X are sums of
-// per-run vectors over the variant's carriers (k_glm_bitdot, GlmParams.ch_bd) and the first Newton step of the ORDINARY likelihood costs a
+// per-run vectors over the variant's carriers (shk_bitdot_i8, GlmParams.ch_bd) and the first Newton step of the ORDINARY likelihood costs a
 // 12 x 12 solve per variant instead of a pass over the samples.  Starting the Firth iteration one step closer saves a whole round (a
 // likelihood pass and a score pass: 12 of 55 ms per C4 batch).  The step is taken in the standardised coordinates of the logistic kernels
 // (warm, null_h, null_g, a0) and mapped back to the columns as given; anything not finite keeps the round-2 start.  A warm slot is marked by
@@ -519,13 +516,8 @@ __global__ __launch_bounds__(512) void k_firth_step2(const uint64_t *__restrict_
             v2f zs[Q];
             {
                 const v2f *zr = zrec + (int64_t)pr * Q;
-#if FIRTH_STEP2_ABL == 2                                                   /* timing ablation: no LDS reads */
-#pragma unroll
-                for (int j = 0; j < Q; ++j) zs[j] = v2f{(float)pr, (float)j};
-#else
 #pragma unroll
                 for (int j = 0; j < Q; ++j) zs[j] = zr[j];
-#endif
             }
             front(ra, xd0, w0, hm0);
             // the wait for rb (and with it for zs) stays BEHIND the first sample's arithmetic: the fence takes that sample's weight as an
@@ -541,11 +533,7 @@ __global__ __launch_bounds__(512) void k_firth_step2(const uint64_t *__restrict_
             front(rb, xd1f, w1, hm1);
 #pragma unroll
             for (int j = 0; j < Q; ++j) asm volatile("" : "+v"(zs[j]) : "v"(w1));   // ... and the hat diagonal behind the second's (no instruction)
-#if FIRTH_STEP2_ABL == 1                                                   /* timing ablation: no hat diagonal */
-            const v2f qf = zs[0];
-#else
             const v2f qf = hat(v2f{(float)b0, (float)b1}, zs);
-#endif
             const v2f h = v2f{(float)w0, (float)w1} * qf;
             back(rc0, xd0, hm0, (double)h.x);
             back(rb, xd1, hm1, (double)h.y);
@@ -637,12 +625,8 @@ extern "C" hipError_t shk_firth2_launch(hipStream_t st, int Q, int which, int64_
     FirthWork fw{fst, fiter, fhalv, fvar, fcap, blk_list, blk_count, s64_list, s64_count};
 #define FIRTH2_CASE(q) case q: return launch_firth2<q>(st, which, n, T, Vpad, V, P, fw, in_list, in_count, next_eval, next_eval_count, step_list, step_count, out, flags, plist, pcount);
     switch (Q) {
-#ifdef FIRTH2_ONLY_Q
-        FIRTH2_CASE(FIRTH2_ONLY_Q)
-#else
         FIRTH2_CASE(1) FIRTH2_CASE(2) FIRTH2_CASE(3) FIRTH2_CASE(4) FIRTH2_CASE(5) FIRTH2_CASE(6) FIRTH2_CASE(7)
         FIRTH2_CASE(8) FIRTH2_CASE(9) FIRTH2_CASE(10) FIRTH2_CASE(11) FIRTH2_CASE(12) FIRTH2_CASE(13) FIRTH2_CASE(14)
-#endif
     default: return hipErrorInvalidValue;
     }
 #undef FIRTH2_CASE

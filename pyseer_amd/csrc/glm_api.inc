@@ -3,7 +3,6 @@
 extern "C" hipError_t shk_glm_launch(hipStream_t, int, int, const uint64_t *, int64_t, int64_t, const double *, const double *, const float *,
                                      const uint64_t *, const uint64_t *, const double *, const double *, const double *, GlmParams,
                                      double *, uint32_t *, int *, int *, int *, int *, double *, int *, int *, int *, int *, int *);
-extern "C" hipError_t shk_bitdot_build_tab(hipStream_t, const double *, int, int, int, double *);
 extern "C" int64_t shk_bitdot_i8_table_bytes(int NE, int NB64);
 extern "C" void shk_bitdot_i8_digits(const double *vals, int N, int NE, int NB64, int8_t *atab, double *scale);
 extern "C" hipError_t shk_glm_ols_tab(hipStream_t, int, int, const uint64_t *, int64_t, int64_t, const double *, const double *, const double *,
@@ -21,7 +20,7 @@ extern "C" int shk_firth_fast_supported(int Q);
 extern "C" int shk_firth_fast_tiles(int Q, int *t2, int *t3, int *rs);
 extern "C" int shk_firth_fast_row2(int Q, int a, int b);
 extern "C" hipError_t shk_firth_fast_launch(hipStream_t, int, int64_t, const uint64_t *, int64_t, GlmParams, double *, int *, int *, int *, int64_t,
-                                            const int *, const int *, int *, int *, int *, int *, int64_t, double *, uint32_t *, int);
+                                            const int *, const int *, int *, int *, int *, int *, int64_t, double *, uint32_t *);
 extern "C" int shk_firth_fastw_layout(int Q, int *t2h, int *t3h, int *rs, int *rows);
 extern "C" hipError_t shk_firth_fastw_launch(hipStream_t, int, int64_t, const uint64_t *, int64_t, GlmParams, double *, int *, int *, int *, int64_t,
                                              const int *, const int *, int *, int *, int *, int *, const uint16_t *, const float *, float *, int64_t);
@@ -45,9 +44,8 @@ struct GlmState {
     double *d_rec = nullptr;            // per-sample records of k_glm_score / k_glm_ll
     double *d_rec_o = nullptr;          // per-sample records of the Firth rounds (covariates as given)
     double *d_rec_f = nullptr; float *d_rec_pf = nullptr;   // firth_rounds.hip: (covariates as given, 1 - 2y) per sample; standardised covariates per pair of samples
-    uint16_t *d_ff_tab = nullptr; double *d_ff_rec = nullptr, *d_ff_inull = nullptr; float *d_ff_rec32 = nullptr;   // firth_fast.hip: monomial tables (halves, hi / lo) and per-sample records
+    uint16_t *d_ff_tab = nullptr; double *d_ff_rec = nullptr, *d_ff_inull = nullptr;   // firth_fast.hip: monomial tables (halves, hi / lo) and per-sample records
     float *d_pk = nullptr;              // pass32_pk tables: wfp [N/2][q][2], yf [N], w0f [N]
-    double *d_bdtab = nullptr;          // nibble tables of the null model's (w0, w0 z, r0): k_glm_bitdot
     int8_t *d_bdi8 = nullptr; double *d_bdscale = nullptr;   // bitdot_i8.hip: digit table and column scales
     double *d_b1 = nullptr;             // constants of the bordered first step (GlmParams.b1)
     double *d_chord = nullptr;          // chord-round workspaces (GlmParams.ch_*), sized with the lists
@@ -69,6 +67,6 @@ static void glm_free(GlmState *g)
 {
     hipFree(g->d_Ws); hipFree(g->d_wstd); hipFree(g->d_Wf); hipFree(g->d_zz); hipFree(g->d_zz16); hipFree(g->d_zl16); hipFree(g->d_olstab); hipFree(g->d_y); hipFree(g->d_W); hipFree(g->d_yc); hipFree(g->d_ZtZ); hipFree(g->d_Zty); hipFree(g->d_y1); hipFree(g->d_y0);
     hipFree(g->d_bw); hipFree(g->d_state); hipFree(g->d_slist); hipFree(g->d_Xlin); hipFree(g->d_lin_out); hipFree(g->d_lin_cof); hipFree(g->d_lin_nc); hipFree(g->d_flist); hipFree(g->d_fcount); hipFree(g->d_plist);
-    hipFree(g->d_fst); hipFree(g->d_fmeta); hipFree(g->d_fl[0]); hipFree(g->d_fl[1]); hipFree(g->d_fl[2]); hipFree(g->d_fl[3]); hipFree(g->d_fl[4]); hipFree(g->d_fcnt); hipFree(g->d_dbg); hipFree(g->d_tile_list); hipFree(g->d_w0); hipFree(g->d_a0); hipFree(g->d_bdi8); hipFree(g->d_bdscale); hipFree(g->d_chord); hipFree(g->d_bdtab); hipFree(g->d_b1); hipFree(g->d_pk); hipFree(g->d_rec); hipFree(g->d_rec_o); hipFree(g->d_rec_f); hipFree(g->d_rec_pf); hipFree(g->d_ff_tab); hipFree(g->d_ff_rec); hipFree(g->d_ff_inull); hipFree(g->d_ff_rec32); hipFree(g->d_ffw_tab); hipFree(g->d_ffw_rec); hipFree(g->d_ffw_ws);
+    hipFree(g->d_fst); hipFree(g->d_fmeta); hipFree(g->d_fl[0]); hipFree(g->d_fl[1]); hipFree(g->d_fl[2]); hipFree(g->d_fl[3]); hipFree(g->d_fl[4]); hipFree(g->d_fcnt); hipFree(g->d_dbg); hipFree(g->d_tile_list); hipFree(g->d_w0); hipFree(g->d_a0); hipFree(g->d_bdi8); hipFree(g->d_bdscale); hipFree(g->d_chord); hipFree(g->d_b1); hipFree(g->d_pk); hipFree(g->d_rec); hipFree(g->d_rec_o); hipFree(g->d_rec_f); hipFree(g->d_rec_pf); hipFree(g->d_ff_tab); hipFree(g->d_ff_rec); hipFree(g->d_ff_inull); hipFree(g->d_ffw_tab); hipFree(g->d_ffw_rec); hipFree(g->d_ffw_ws);
     *g = GlmState();
 }

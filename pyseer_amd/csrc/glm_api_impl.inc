@@ -5,6 +5,7 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
 {
     if (!c || !y || (q > 0 && !W)) return fail(SH_EINVAL, "null argument");
     if (q < 0 || q > 32) return fail(SH_EINVAL, "q (MDS components + covariates) must be 0..32 in this build");
+    if (const char *ce = sh_route("bitdot")) if (std::atoi(ce) == 2) return fail(SH_EINVAL, "SEERHIP_ROUTE: bitdot=2 is not a route of this build (keys: csrc/route.h)");
     const bool wide = q > 14;                             // glm_wide.hip: run-time width on scratch arrays
     HIPCHK(hipSetDevice(c->device));
     { const int rc0 = drain_pending(c); if (rc0) return rc0; }        // a batch still in flight belongs to the model being replaced
@@ -177,7 +178,7 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
             HIPCHK(dmalloc(&g.d_w0, N)); HIPCHK(dmalloc(&g.d_a0, a0.size()));
             HIPCHK(hipMemcpy(g.d_w0, w0.data(), sizeof(double) * N, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(g.d_a0, a0.data(), sizeof(double) * a0.size(), hipMemcpyHostToDevice));
-            // per-sample (w0, w0 z, r0) for the carrier sums (k_glm_bitdot), the rest of the null model's information matrix and its score
+            // per-sample (w0, w0 z, r0) for the carrier sums (bitdot_i8.hip), the rest of the null model's information matrix and its score
             const int NE = q + 2;
             std::vector<double> vals((size_t)N * NE);
             for (int a = 0; a < 16; ++a) { P.null_h[a] = 0.0; P.null_g[a] = 0.0; }
@@ -246,13 +247,7 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
                     HIPCHK(hipMemcpy(g.d_b1, b1.data(), sizeof(double) * b1.size(), hipMemcpyHostToDevice));
                 }
             }
-            double *d_vals = nullptr;
-            HIPCHK(dmalloc(&d_vals, vals.size())); HIPCHK(dmalloc(&g.d_bdtab, (size_t)c->NB64 * 256 * NE));
-            HIPCHK(hipMemcpy(d_vals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
-            HIPCHK(shk_bitdot_build_tab(st, d_vals, NE, N, c->NB64, g.d_bdtab));
-            HIPCHK(hipStreamSynchronize(st));
-            hipFree(d_vals);
-            {   // the same table as base-256 digits for the int8 matrix cores (bitdot_i8.hip)
+            {   // the table of the carrier sums: base-256 digits for the int8 matrix cores (bitdot_i8.hip)
                 std::vector<int8_t> at((size_t)shk_bitdot_i8_table_bytes(NE, c->NB64));
                 std::vector<double> sc((size_t)4 * ((NE + 3) / 4));
                 shk_bitdot_i8_digits(vals.data(), N, NE, c->NB64, at.data(), sc.data());
@@ -307,14 +302,12 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
     if (const char *ce = sh_route("chord_enter")) P.chord_enter = std::atof(ce);
     P.chord_tol = 2.5e-7;
     // the first step from carrier sums and the finishing kernels need the null-model tables (built with w0 / a0 above)
-    P.bd_tab = (P.chord_on && g.d_bdtab && P.a0 && P.w0) ? g.d_bdtab : nullptr;
-    if (const char *ce = sh_route("bitdot")) if (std::atoi(ce) == 0) P.bd_tab = nullptr;
-    P.bd_i8 = (P.bd_tab && g.d_bdi8 && g.d_bdscale) ? g.d_bdi8 : nullptr; P.bd_scale = g.d_bdscale;
-    if (const char *ce = sh_route("bitdot")) if (std::atoi(ce) == 2) P.bd_i8 = nullptr;              // 2: the nibble-table kernel of round 3
-    P.b1 = (P.bd_tab && g.d_b1 && P.chord_n32 > 1) ? g.d_b1 : nullptr;     // (a single Newton round has no next round to hand a small first step to)
+    P.bd_i8 = (P.chord_on && g.d_bdi8 && g.d_bdscale && P.a0 && P.w0) ? g.d_bdi8 : nullptr; P.bd_scale = g.d_bdscale;
+    if (const char *ce = sh_route("bitdot")) if (std::atoi(ce) == 0) P.bd_i8 = nullptr;
+    P.b1 = (P.bd_i8 && g.d_b1 && P.chord_n32 > 1) ? g.d_b1 : nullptr;     // (a single Newton round has no next round to hand a small first step to)
     if (const char *ce = sh_route("first_bordered")) if (std::atoi(ce) == 0) P.b1 = nullptr;
     P.wfp = P.yf = P.w0f = nullptr;
-    if (P.bd_tab && g.d_pk && !(sh_route("pk") && std::atoi(sh_route("pk")) == 0)) {
+    if (P.bd_i8 && g.d_pk && !(sh_route("pk") && std::atoi(sh_route("pk")) == 0)) {
         P.wfp = g.d_pk; P.yf = g.d_pk + (size_t)(N / 2) * (q + 2) * 2; P.w0f = P.yf + N + (N & 1);
     }
     P.rec = g.d_rec;
@@ -346,13 +339,13 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
         }
     }
     if (!P.rec) P.chord_on = 0;
-    // Firth rounds one Newton step ahead of the null-model fit (k_firth_init2): needs the carrier sums of the logistic rounds (k_glm_bitdot runs
-    // whenever chord_on and bd_tab are set) and the round-3 kernels.
-    if (P.firth_warm == 1 && P.chord_on && P.bd_tab && P.a0 && P.rec_f)
+    // Firth rounds one Newton step ahead of the null-model fit (k_firth_init2): needs the carrier sums of the logistic rounds (shk_bitdot_i8 runs
+    // whenever chord_on and bd_i8 are set) and the round-3 kernels.
+    if (P.firth_warm == 1 && P.chord_on && P.bd_i8 && P.a0 && P.rec_f)
         P.firth_warm = 2;
     // The one-pass iteration (firth_fast.hip) where the rounds start warm (every variant through fit_firth at N >= 4096, centred covariates,
     // default noise rules) and the third-moment tensor fits the accumulators (Q <= 10).  SEERHIP_ROUTE firth_fast=0: the two-pass rounds only.
-    P.ff_tab = nullptr; P.ff_rec = nullptr; P.ff_inull = nullptr; P.ff_rec32 = nullptr;
+    P.ff_tab = nullptr; P.ff_rec = nullptr; P.ff_inull = nullptr;
     if (P.firth_warm == 2 && P.firth_noise > 0.0 && shk_firth_fast_supported(q) &&
         !(sh_route("firth_fast") && std::atoi(sh_route("firth_fast")) == 0)) {
         int t2 = 0, t3 = 0, rs = 0;
@@ -420,13 +413,7 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
         HIPCHK(dmalloc(&g.d_ff_tab, tab.size())); HIPCHK(dmalloc(&g.d_ff_rec, rec.size()));
         HIPCHK(hipMemcpy(g.d_ff_tab, tab.data(), sizeof(uint16_t) * tab.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(g.d_ff_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
-        {   // the records in single precision, slot for slot (a record keeps its rs * 8 bytes: one staging layout for both passes)
-            std::vector<float> rec32(rec.size() * 2, 0.0f);
-            for (size_t i = 0; i < (size_t)NG * 16; ++i) for (int j = 0; j < rs; ++j) rec32[i * (size_t)rs * 2 + j] = (float)rec[i * (size_t)rs + j];
-            HIPCHK(dmalloc(&g.d_ff_rec32, rec32.size()));
-            HIPCHK(hipMemcpy(g.d_ff_rec32, rec32.data(), sizeof(float) * rec32.size(), hipMemcpyHostToDevice));
-        }
-        if (!(sh_route("firth_w") && std::atoi(sh_route("firth_w")) == 0)) {
+        {
             // firth_fast_w.hip: the same monomials as 16-row tiles of 32-sample groups (hi halves only: the single-precision pass takes one
             // product per tile), lane (m = lane & 15, kq = lane >> 4) = row m, samples 32 g + 8 kq .. + 7; records (z_s, s, -2^12 w0) as floats
             int t2h = 0, t3h = 0, rsw = 0, rows = 0;
@@ -452,11 +439,11 @@ int sh_glm_setup(sh_ctx *c, const double *y, const double *W, int q, int continu
         }
         HIPCHK(dmalloc(&g.d_ff_inull, inull.size()));
         HIPCHK(hipMemcpy(g.d_ff_inull, inull.data(), sizeof(double) * inull.size(), hipMemcpyHostToDevice));
-        P.ff_tab = g.d_ff_tab; P.ff_rec = g.d_ff_rec; P.ff_inull = g.d_ff_inull; P.ff_rec32 = g.d_ff_rec32;
+        P.ff_tab = g.d_ff_tab; P.ff_rec = g.d_ff_rec; P.ff_inull = g.d_ff_inull;
     }
     // the finishing kernels take y in {0, 1} (k_glm_ll); anything else keeps k_glm_final, which mirrors statsmodels' general formula
     bool ybin = true; for (int i = 0; i < N; ++i) ybin = ybin && (y[i] == 0.0 || y[i] == 1.0);
-    P.fin_rounds = (P.bd_tab != nullptr && ybin) ? 1 : 0;
+    P.fin_rounds = (P.bd_i8 != nullptr && ybin) ? 1 : 0;
     if (const char *ce = sh_route("fin_rounds")) P.fin_rounds = P.fin_rounds && std::atoi(ce) != 0;
     P.ll_first = P.fin_rounds;                                       // SEERHIP_ROUTE ll_first=0: score pass first, likelihood pass last (rounds 2 - 3a)
     if (const char *ce = sh_route("ll_first")) P.ll_first = P.ll_first && std::atoi(ce) != 0;
@@ -542,12 +529,11 @@ static int firth_rounds(sh_ctx *c, int64_t Vpad, int64_t V, const GlmParams &P, 
         // Round 6: TWO single-precision passes at two wavefronts per SIMD (2 x 2.8 ms), then ONE fp64 pass that finds a last step of ~1e-8
         // and finishes the fit (6 ms) -- instead of one + two (the second fp64 pass only took the fit from 1e-5 to 1e-8 of its fixed point).
         // What made the second single-precision pass land within 1e-7: its sums in double precision across groups, and the next candidate
-        // formed from the point the pass really evaluated (firth_fast_w.hip).  The one-wavefront kernel (firth_w=0) has neither: one pass.
-        const int ff_first32 = g.d_ffw_tab ? g.ff_first32 : std::min(g.ff_first32, 1);
+        // formed from the point the pass really evaluated (firth_fast_w.hip).
         while (nF > 0) {
             HIPCHK(hipMemsetAsync(cFb, 0, sizeof(int), st));
-            // (the first pass, at the start vector, in single precision: its step is 1e-5 from the fit at best, firth_fast.hip)
-            if (passes < ff_first32 && g.d_ffw_tab) {
+            // (the first pass, at the start vector, in single precision: its step is 1e-5 from the fit at best)
+            if (passes < g.ff_first32) {
                 // (the first pass at two wavefronts per SIMD: firth_fast_w.hip; its sums cross to the per-fit kernel through the workspace)
                 if (nF > g.ffw_cap) {
                     hipFree(g.d_ffw_ws); g.d_ffw_ws = nullptr; g.ffw_cap = 0;
@@ -559,8 +545,7 @@ static int firth_rounds(sh_ctx *c, int64_t Vpad, int64_t V, const GlmParams &P, 
                 HIPCHK(shk_firth_fastw_launch(st, g.q, nF, c->d_T, Vpad, P, g.d_fst, it, hv, vr, g.fcap, Fa, cFa, Fb, cFb, X, cX, g.d_ffw_tab, g.d_ffw_rec,
                                               g.d_ffw_ws, g.ffw_cap));
             } else
-            HIPCHK(shk_firth_fast_launch(st, g.q, nF, c->d_T, Vpad, P, g.d_fst, it, hv, vr, g.fcap, Fa, cFa, Fb, cFb, X, cX, V, d_out, d_flags,
-                                         passes < ff_first32 ? 1 : 0));
+                HIPCHK(shk_firth_fast_launch(st, g.q, nF, c->d_T, Vpad, P, g.d_fst, it, hv, vr, g.fcap, Fa, cFa, Fb, cFb, X, cX, V, d_out, d_flags));
             { int two[2] = {0, 0}; const int rcb = readback_sync(c, st, cFb, cX, nullptr, nullptr, two); if (rcb) return rcb; nF = two[0]; nE = two[1]; }
             if (dbg) fprintf(stderr, "[firth debug] one-pass round %d: %d go on\n", passes, nF);
             ++passes;

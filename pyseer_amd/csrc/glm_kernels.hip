@@ -197,185 +197,7 @@ __device__ __forceinline__ float weight_even(float eta)
     const float a = t * m;                                            // = min(mu, 1 - mu) <= 1/2: a - a^2 does not cancel, and is as insensitive to the
     return __builtin_fmaf(-a, a, a);                                  // error of the reciprocal near mu = 1/2 as mu - mu^2 is (most samples)
 }
-template <int Q, bool DELTA>
-__device__ __forceinline__ void pass32_pk_f32(const uint64_t *__restrict__ T, int64_t Vpad, int64_t v, const GlmParams &P, const float *__restrict__ Wf,
-                                          const double (&beta)[Q + 2], float (&H)[(Q + 2) * (Q + 3) / 2], double (&g)[Q + 2], float *tr,
-                                          int part = 0, int nparts = 1, double *hdl = nullptr)
-{
-    // hdl (DELTA): [2 + 2Q][64] doubles of LDS, zeroed by the caller.  The intercept and variant rows of X^T (W - W0) X are summed in single
-    // precision WITHIN a 64-sample word and in double precision across words: for a variant with a large effect (|beta| ~ 4) the differences
-    // w - w0 of its carriers are ~0.2 each, their running sum reaches hundreds, and 2500 fp32 additions at that magnitude put 1e-6 on the
-    // variant's own diagonal entry, i.e. on bse (measured on near-separating variants at N = 5000: 1.7e-6 against the fp64 restatement).
-    // part / nparts: this wavefront's share of the samples (k_glm_pass32_split): whole 64-sample words [wd0, wd1); the last part also takes
-    // the partial word and the odd sample
-    constexpr int PC = Q + 2, NCB = FastCols<Q>::NCB, STRIDE = FastCols<Q>::STRIDE;
-    const int N = P.N;
-    const int lane = threadIdx.x & 63, lh = lane >> 5, l31 = lane & 31;
-    const float *__restrict__ ZZ = P.zz;
-    // per pair of samples one wave-uniform record: z (Q float2), y pair, w0 pair -- fetched one pair AHEAD (scalar loads otherwise sit
-    // exposed in front of every pair: ~900 cycles per pair and wavefront, measured), as is the lane's B operand of the MFMA
-    constexpr int RS = Q + 2;
-    const v2f *__restrict__ Rp = (const v2f *)P.wfp;
-    v16f acc[NCB][2];
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[cb][h][r] = 0.0f;
-    v2f bf[PC], gf[PC], h00 = {0.0f, 0.0f}, h10 = {0.0f, 0.0f}, hz0[Q > 0 ? Q : 1], hz1[Q > 0 ? Q : 1];
-#pragma unroll
-    for (int a = 0; a < PC; ++a) { const float b = (float)beta[a]; bf[a] = v2f{b, b}; gf[a] = v2f{0.0f, 0.0f}; }
-    const EtaConst ec = eta_const(beta[0], beta[1]);                        // (DELTA only: the constants of eta with their lo parts)
-    const float vsub = fabs(beta[0] + beta[1] - P.warm[0]) >= GLM_DIRECT_ROW ? 0.0f : -1.0f;      // (DELTA only: the variant's row sums w - w0, or w itself)
-#pragma unroll
-    for (int j = 0; j < Q; ++j) { hz0[j] = v2f{0.0f, 0.0f}; hz1[j] = v2f{0.0f, 0.0f}; }
-    const int nfull = N >> 1;
-    auto pair = [&](const v2f (&rec)[RS], const float (&bz)[NCB], uint32_t two) {
-        const v2f xb = {(float)(two & 1u), (float)(two >> 1)};
-        v2f eta = DELTA ? pkfma(xb, v2f{ec.dl, ec.dl}, v2f{ec.lo0, ec.lo0}) : pkfma(xb, bf[1], bf[0]);
-#pragma unroll
-        for (int j = 0; j < Q; ++j) eta = pkfma(bf[2 + j], rec[j], eta);
-        if (DELTA) eta = eta + pkfma(xb, v2f{ec.dh, ec.dh}, v2f{ec.c0h, ec.c0h});
-        v2f mu, wf;
-        if (DELTA) { wf.x = weight_even(eta.x); wf.y = weight_even(eta.y); }
-        else { mu.x = sigmoid_fast(eta.x); mu.y = sigmoid_fast(eta.y); wf = pkfma(-mu, mu, mu); }
-        v2f d = wf;
-        if (DELTA) d = wf - rec[Q + 1];
-        else {
-            const v2f r = rec[Q] - mu;
-            gf[0] += r; gf[1] = pkfma(xb, r, gf[1]);
-#pragma unroll
-            for (int j = 0; j < Q; ++j) gf[2 + j] = pkfma(r, rec[j], gf[2 + j]);
-        }
-        const v2f dx = xb * (DELTA ? pkfma(v2f{vsub, vsub}, rec[Q + 1], wf) : d);
-        h00 += d; h10 += dx;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) { hz0[j] = pkfma(d, rec[j], hz0[j]); hz1[j] = pkfma(dx, rec[j], hz1[j]); }
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d.x), __float_as_uint(d.y), false, false);
-        const float a0f = __uint_as_float(sw[0]), a1f = __uint_as_float(sw[1]);
-#ifndef P32_ABL_NO_MFMA                                                  /* timing ablation (results meaningless): the pass without its MFMAs */
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            acc[cb][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0f, bz[cb], acc[cb][0], 0, 0, 0);
-            acc[cb][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1f, bz[cb], acc[cb][1], 0, 0, 0);
-        }
-#else
-        acc[0][0][0] += a0f * bz[0]; acc[0][1][0] += a1f * bz[NCB - 1];
-#endif
-    };
-    auto fetch_rec = [&](int pr, v2f (&rec)[RS]) {
-#pragma unroll
-        for (int k = 0; k < RS; ++k) rec[k] = Rp[(int64_t)pr * RS + k];
-    };
-    auto fetch_bz = [&](int pr, float (&bz)[NCB]) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) bz[cb] = ZZ[(int64_t)(2 * pr + lh) * STRIDE + l31 + cb * 32];
-    };
-    // Records: two buffers in turn, pair p + 1 fetched while pair p is computed (scalar loads, ordered by pipe_zero).  The lane's B operands
-    // come from L2 (the products table is 1.3 MB at N = 5000): four buffers, fetched two pairs ahead.  A 64-sample word holds 32 pairs.
-    v2f ra[RS], rb[RS];
-    float za[NCB], zb[NCB], zc[NCB], zd[NCB];
-    const int nwords = nfull >> 5;                                            // whole words: pipelined
-    const int plast = nfull > 0 ? nfull - 1 : 0;
-    const int wd0 = (int)((int64_t)nwords * part / nparts), wd1 = (int)((int64_t)nwords * (part + 1) / nparts);
-    const bool tail = part == nparts - 1;
-    fetch_rec(min(wd0 * 32, plast), ra); fetch_bz(min(wd0 * 32, plast), za); fetch_bz(min(wd0 * 32 + 1, plast), zb);
-    uint64_t w = T[(int64_t)min(wd0, (N - 1) >> 6) * Vpad + v];
-    for (int wd = wd0; wd < wd1; ++wd) {
-        const uint64_t wn = T[(int64_t)min(wd + 1, (N - 1) >> 6) * Vpad + v];
-        for (int k = 0; k < 32; k += 2) {
-            const int pr = wd * 32 + k;
-            fetch_bz(min(pr + 2, plast), zc); fetch_bz(min(pr + 3, plast), zd);
-            fetch_rec(pr + 1 + pipe_zero(ra[0].x), rb);
-            pair(ra, za, (uint32_t)(w >> (2 * k)) & 3u);
-            fetch_rec(min(pr + 2, plast) + pipe_zero(rb[0].x), ra);
-            pair(rb, zb, (uint32_t)(w >> (2 * k + 2)) & 3u);
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) { za[cb] = zc[cb]; zb[cb] = zd[cb]; }
-        }
-        w = wn;
-        if (DELTA && hdl) {
-            hdl[lane] += (double)(h00.x + h00.y); hdl[64 + lane] += (double)(h10.x + h10.y);
-            h00 = v2f{0.0f, 0.0f}; h10 = v2f{0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < Q; ++j) {
-                hdl[(2 + j) * 64 + lane] += (double)(hz0[j].x + hz0[j].y); hdl[(2 + Q + j) * 64 + lane] += (double)(hz1[j].x + hz1[j].y);
-                hz0[j] = v2f{0.0f, 0.0f}; hz1[j] = v2f{0.0f, 0.0f};
-            }
-        }
-    }
-    for (int pr = nwords * 32; tail && pr < nfull; ++pr) {                    // the last partial word, plainly
-        if (pr == nwords * 32) w = T[(int64_t)(pr >> 5) * Vpad + v];
-        fetch_rec(pr, ra); fetch_bz(pr, za);
-        pair(ra, za, (uint32_t)(w >> (2 * (pr & 31))) & 3u);
-    }
-    float h00s = h00.x + h00.y, h10s = h10.x + h10.y, gs[PC], hz0s[Q > 0 ? Q : 1], hz1s[Q > 0 ? Q : 1];
-#pragma unroll
-    for (int a = 0; a < PC; ++a) gs[a] = gf[a].x + gf[a].y;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) { hz0s[j] = hz0[j].x + hz0[j].y; hz1s[j] = hz1[j].x + hz1[j].y; }
-    if ((N & 1) && tail) {                                                    // the odd sample: k = 1 rows of A are zero
-        const int i = N - 1;
-        const float *zrow = ZZ + (int64_t)i * STRIDE + l31;
-        const bool xb = (T[(int64_t)(i >> 6) * Vpad + v] >> (i & 63)) & 1ull;
-        float eta = DELTA ? ec.lo0 + (xb ? ec.dl : 0.0f) : bf[0].x + (xb ? bf[1].x : 0.0f);
-#pragma unroll
-        for (int j = 0; j < Q; ++j) eta = fmaf(bf[2 + j].x, Wf[(int64_t)i * Q + j], eta);
-        if (DELTA) eta += fmaf(xb ? 1.0f : 0.0f, ec.dh, ec.c0h);
-        const float mu = sigmoid_fast(eta);
-        const float wf = DELTA ? weight_even(eta) : mu * (1.0f - mu);
-        float d = wf;
-        if (DELTA) d = wf - P.w0f[i];
-        else {
-            const float r = P.yf[i] - mu;
-            gs[0] += r; gs[1] += xb ? r : 0.0f;
-#pragma unroll
-            for (int j = 0; j < Q; ++j) gs[2 + j] = fmaf(r, Wf[(int64_t)i * Q + j], gs[2 + j]);
-        }
-        const float dx = xb ? (DELTA ? fmaf(vsub, P.w0f[i], wf) : d) : 0.0f;
-        h00s += d; h10s += dx;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) { const float zj = Wf[(int64_t)i * Q + j]; hz0s[j] = fmaf(d, zj, hz0s[j]); hz1s[j] = fmaf(dx, zj, hz1s[j]); }
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d), 0u, false, false);
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            acc[cb][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(sw[0]), zrow[cb * 32], acc[cb][0], 0, 0, 0);
-            acc[cb][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(sw[1]), zrow[cb * 32], acc[cb][1], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < PC; ++a) g[a] = (double)gs[a];
-    if (DELTA && hdl) {
-        h00s = (float)(hdl[lane] + (double)h00s); h10s = (float)(hdl[64 + lane] + (double)h10s);
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            hz0s[j] = (float)(hdl[(2 + j) * 64 + lane] + (double)hz0s[j]); hz1s[j] = (float)(hdl[(2 + Q + j) * 64 + lane] + (double)hz1s[j]);
-        }
-    }
-    H[sidx(0, 0)] = h00s; H[sidx(1, 0)] = h10s; H[sidx(1, 1)] = h10s;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) { H[sidx(2 + j, 0)] = hz0s[j]; H[sidx(2 + j, 1)] = hz1s[j]; }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        __syncthreads();
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * lh) * (STRIDE + 1) + cb * 32 + l31] = acc[cb][h][r];
-        __syncthreads();
-        if (lh == h) {
-            const float *row = tr + l31 * (STRIDE + 1);
-#pragma unroll
-            for (int j = 0; j < Q; ++j)
-#pragma unroll
-                for (int k = 0; k <= j; ++k) H[sidx(2 + j, 2 + k)] = row[j * (j + 1) / 2 + k];
-        }
-    }
-}
-
-
-// ---- the same pass with the covariate block on the HALF-precision matrix pipe (round 3) ---------------------------------------------------
+// ---- the covariate block of the pass on the HALF-precision matrix pipe (round 3) ---------------------------------------------------------
 // Measured in round 3 (timing build without the MFMAs): the four v_mfma_f32_32x32x2_f32 per pair of samples cost 1.2 of the 3.15 ms of
 // k_glm_pass32 -- on gfx950 an f32 MFMA runs on the vector ALUs' rate and its time ADDS to the VALU's.  The f16 MFMA
 // (v_mfma_f32_32x32x16_f16) runs on the matrix cores proper, 16x the MAC rate: 16 samples per issue instead of 2.
@@ -393,18 +215,17 @@ typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 #define P32_ASCALE 1024.0f
-#ifndef P16_ABL
-#define P16_ABL 0
-#endif
-#ifndef P16_ABL_D
-#define P16_ABL_D 0
-#endif
 template <int Q, bool DELTA>
 __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, int64_t Vpad, int64_t v, const GlmParams &P, const float *__restrict__ Wf,
                                           const double (&beta)[Q + 2], float (&H)[(Q + 2) * (Q + 3) / 2], double (&g)[Q + 2], float *tr,
                                           int part = 0, int nparts = 1, double *hdl = nullptr)
 {
-    // hdl, part / nparts: as pass32_pk_f32 above
+    // hdl (DELTA): [2 + 2Q][64] doubles of LDS, zeroed by the caller.  The intercept and variant rows of X^T (W - W0) X are summed in single
+    // precision WITHIN a 64-sample word and in double precision across words: for a variant with a large effect (|beta| ~ 4) the differences
+    // w - w0 of its carriers are ~0.2 each, their running sum reaches hundreds, and 2500 fp32 additions at that magnitude put 1e-6 on the
+    // variant's own diagonal entry, i.e. on bse (measured on near-separating variants at N = 5000: 1.7e-6 against the fp64 restatement).
+    // part / nparts: this wavefront's share of the samples (k_glm_pass32_split): whole 64-sample words [wd0, wd1); the last part also takes
+    // the partial word and the odd sample
     constexpr int PC = Q + 2, NCB = FastCols<Q>::NCB, STRIDE = FastCols<Q>::STRIDE, NPART = DELTA ? 2 : 1;
     // Round 5: the table's spare columns (STRIDE - NPROD: 9 at Q = 10) hold z_j itself, so the intercept row's entries sum (w) z_j come out of the
     // same MFMAs as the block's (column NPROD + j), at the block's precision, instead of a packed fma per pair and entry on the vector ALU
@@ -429,9 +250,6 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
     const int N = P.N;
     const int lane = threadIdx.x & 63, lh = lane >> 5, l31 = lane & 31;
     constexpr int RS = Q + 2;
-    // timing ablations (results meaningless; profiles/r05/pass32_ablations.txt): 1 no MFMAs, 2 no table loads, 4 no transcendentals, 8 no score,
-    // 16 every record load reads record 0 (always a scalar-cache hit)
-    constexpr int ABL = DELTA ? P16_ABL_D : P16_ABL;
     // (constant address space: the touches below are volatile asm, which would otherwise take the "never clobbered" property from the records
     // and turn their scalar loads into per-lane vector loads -- firth_rounds.hip)
     typedef const __attribute__((address_space(4))) v2f *crec_t;
@@ -488,12 +306,10 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
         for (int j = 0; j < Q; ++j) eta = pkfma(bf[2 + j], rec[j], eta);
         if (DELTA) eta = eta + pkfma(xb, v2f{ec.dh, ec.dh}, v2f{ec.c0h, ec.c0h});
         v2f mu, wf;
-        if (ABL & 4) { mu = pkfma(eta, v2f{0.25f, 0.25f}, v2f{0.5f, 0.5f}); wf = pkfma(-mu, mu, mu); }
-        else if (DELTA) { wf.x = weight_even(eta.x); wf.y = weight_even(eta.y); }
+        if (DELTA) { wf.x = weight_even(eta.x); wf.y = weight_even(eta.y); }
         else { mu.x = sigmoid_fast(eta.x); mu.y = sigmoid_fast(eta.y); wf = pkfma(-mu, mu, mu); }
         v2f d = wf;
         if (DELTA) d = wf - rec[Q + 1];
-        else if (ABL & 8) { gf[0] += rec[Q] - mu; }
         else {
             const v2f r = rec[Q] - mu;
             gf[0] += r; gf[1] = pkfma(xb, r, gf[1]);
@@ -510,13 +326,13 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
     };
     auto fetch_rec = [&](int pr, v2f (&rec)[RS]) {
 #pragma unroll
-        for (int k = 0; k < RS; ++k) rec[k] = Rp[(int64_t)((ABL & 16) ? 0 : pr) * RS + k];
+        for (int k = 0; k < RS; ++k) rec[k] = Rp[(int64_t)pr * RS + k];
     };
     auto fetch_bz = [&](int grp, v4u (&bz)[NCB][NPART]) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-            for (int q2 = 0; q2 < NPART; ++q2) bz[cb][q2] = (ABL & 2) ? v4u{(uint32_t)grp, 0u, 0u, 0u} : Z16[(((int64_t)grp * NCB + cb) * 2 + q2) * 64 + lane];
+            for (int q2 = 0; q2 < NPART; ++q2) bz[cb][q2] = Z16[(((int64_t)grp * NCB + cb) * 2 + q2) * 64 + lane];
     };
     auto fetch_bl = [&](int grp, v4u &bl) { if constexpr (LIN) bl = ZL[(int64_t)grp * 64 + lane]; };
     // the group's w k against the linear block (operands swapped into place as the weights' are)
@@ -535,7 +351,6 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
     };
     // the 16 samples stashed in Ah / Al against the group's product columns
     auto flush = [&](const v4u (&bz)[NCB][NPART]) {
-        if (ABL & 1) { acc[0][0][0] += __builtin_bit_cast(float, Ah[0] ^ Ah[7] ^ bz[0][0][0] ^ bz[NCB - 1][NPART - 1][0]) + (DELTA ? __builtin_bit_cast(float, Al[0]) : 0.0f); return; }
         v4u a0, a1, l0, l1;
 #pragma unroll
         for (int q2 = 0; q2 < 4; ++q2) {
@@ -586,7 +401,7 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
                 fetch_rec(pr + 1 + pipe_zero(ra[0].x), rb);
                 // (the touches go out BEHIND the wait for this pair's record and the request for the next one: issued in front of that wait
                 // they were waited for at once -- a whole miss exposed per group instead of a miss less a pair's arithmetic)
-                if (TOUCH && k == 0 && !(ABL & 32)) touch_group(min(grp + 1, (plast >> 3)), 0, RS);
+                if (TOUCH && k == 0) touch_group(min(grp + 1, (plast >> 3)), 0, RS);
                 pair(ra, k, (wbits >> (2 * k)) & 3u);
                 fetch_rec(min(pr + 2, plast) + pipe_zero(rb[0].x), ra);
                 pair(rb, k + 1, (wbits >> (2 * k + 2)) & 3u);
@@ -708,19 +523,16 @@ __device__ __forceinline__ void pass32_pk_f16(const uint64_t *__restrict__ T, in
     for (int a = 0; a < PC; ++a) g[a] = (double)gs[a];
 }
 
-#ifndef P32_F16
-#define P32_F16 1                    /* 0: the covariate block of the packed passes on the f32 MFMA (round 2), for A/B */
-#endif
+// The kernels reach the pass through this forwarding function, and it is not decoration: the compiler optimises the pass once more after
+// inlining it here, before the kernels inline the result.  Calling pass32_pk_f16 directly allocates registers differently in every kernel that
+// holds the pass (k_glm_pass32, k_glm_pass32_split, k_glm_dpass_pk: at Q = 6 three wavefronts per SIMD instead of two, at Q = 13 more scratch)
+// and measured 2 - 6 % slower at Q = 6, 7 and 13.
 template <int Q, bool DELTA>
 __device__ __forceinline__ void pass32_pk(const uint64_t *__restrict__ T, int64_t Vpad, int64_t v, const GlmParams &P, const float *__restrict__ Wf,
                                           const double (&beta)[Q + 2], float (&H)[(Q + 2) * (Q + 3) / 2], double (&g)[Q + 2], float *tr,
                                           int part = 0, int nparts = 1, double *hdl = nullptr)
 {
-#if P32_F16
     pass32_pk_f16<Q, DELTA>(T, Vpad, v, P, Wf, beta, H, g, tr, part, nparts, hdl);
-#else
-    pass32_pk_f32<Q, DELTA>(T, Vpad, v, P, Wf, beta, H, g, tr, part, nparts, hdl);
-#endif
 }
 
 // ---- the fast phase as ROUNDS of lean kernels over lists of variants (GlmParams.chord_on) -------------------------------------
@@ -872,7 +684,7 @@ __global__ __launch_bounds__(256) void k_glm_solve32(int64_t Vpad, GlmParams P, 
         if (FIRST) {
             // the step from the warm start needs no pass over the samples: there eta_i is the NULL model's, so w_i = w0_i and r_i = r0_i do
             // not depend on the variant, and the variant's row of X^T W X and its score are sums of per-run vectors over the carriers
-            // (k_glm_bitdot); the [1, z] block is the null model's (null_h, a0).  All fp64.
+            // (shk_bitdot_i8); the [1, z] block is the null model's (null_h, a0).  All fp64.
             A[sidx(0, 0)] = P.null_h[0]; A[sidx(1, 0)] = A[sidx(1, 1)] = P.ch_bd[v];
             g[0] = P.null_g[0]; g[1] = P.ch_bd[(int64_t)(Q + 1) * Vpad + v];
 #pragma unroll
@@ -1163,57 +975,7 @@ __global__ __launch_bounds__(256) void k_glm_chord(int64_t Vpad, GlmParams P, Gl
     list_push_block(go_direct, P.ch_list[5], P.ch_cnt + 29, (int)v, push_lds);
 }
 
-// ---- sums of per-run vectors over a variant's carriers, by nibble table (the device of k_glm_ols_tab) --------------------------
-// vals[i][c], c < NE = Q + 2: (w0_i, w0_i z_i0 .. w0_i z_i,Q-1, r0_i) at the null model.  tab[(sb * 16 + nib) * 16 + value][c] = the sum
-// over the set bits of `value` of the four samples of nibble `nib` of word `sb`.
-__global__ __launch_bounds__(256) void k_bitdot_build_tab(const double *__restrict__ vals, int NE, int N, int NB64, double *__restrict__ tab)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= NB64 * 256) return;
-    const int value = e & 15, base = (e >> 4) * 4;
-    for (int c = 0; c < NE; ++c) {
-        double a = 0.0;
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k;
-            if (((value >> k) & 1) && i < N) a += vals[(int64_t)i * NE + c];
-        }
-        tab[(int64_t)e * NE + c] = a;
-    }
-}
-
 extern "C" hipError_t shk_bitdot_i8(hipStream_t st, const uint64_t *T, int64_t Vpad, int NB64, int NE, const void *atab, const double *scale, double *out);
-template <int Q>
-__global__ __launch_bounds__(256) void k_glm_bitdot(const uint64_t *__restrict__ T, int64_t Vpad, GlmParams P)
-{
-    constexpr int NE = Q + 2;
-    __shared__ __attribute__((aligned(16))) double lt[2][256 * NE];
-    const int tid = threadIdx.x;
-    const int64_t v = (int64_t)blockIdx.x * 256 + tid;               // Vpad is a multiple of 256: every thread walks (rows >= V are zero)
-    const int NB64 = P.NB64;
-    const double *__restrict__ tab = P.bd_tab;
-    double acc[NE];
-#pragma unroll
-    for (int c = 0; c < NE; ++c) { acc[c] = 0.0; lt[0][tid * NE + c] = tab[(int64_t)tid * NE + c]; }
-    for (int sb = 0; sb < NB64; sb++) {
-        double nxt[NE];
-        const bool more = sb + 1 < NB64;
-#pragma unroll
-        for (int c = 0; c < NE; ++c) nxt[c] = more ? tab[((int64_t)(sb + 1) * 256 + tid) * NE + c] : 0.0;
-        const uint64_t w = T[(int64_t)sb * Vpad + v];
-        __syncthreads();
-        const double *cur = lt[sb & 1];
-#pragma unroll 4
-        for (int nib = 0; nib < 16; ++nib) {
-            const double *e = cur + (nib * 16 + (int)((w >> (4 * nib)) & 15ull)) * NE;
-#pragma unroll
-            for (int c = 0; c < NE; ++c) acc[c] += e[c];
-        }
-#pragma unroll
-        for (int c = 0; c < NE; ++c) lt[(sb + 1) & 1][tid * NE + c] = nxt[c];
-    }
-#pragma unroll
-    for (int c = 0; c < NE; ++c) P.ch_bd[(int64_t)c * Vpad + v] = acc[c];
-}
 
 // the decisions of model.py:332-344, 384 on a finished fit, and its output row (shared by k_glm_final and k_glm_finish)
 template <int Q>
@@ -1442,7 +1204,7 @@ __global__ __launch_bounds__(64, 2) void k_glm_final(const uint64_t *__restrict_
 //   k_glm_ll      fp64: eta, mu, the log-likelihood, the separation callback's max |y - mu| and the score        (~70 VGPRs)
 //   k_glm_dpass   fp32: X^T (W - W0) X, every entry a difference from the null model's -- the z x z block on the matrix pipe against the
 //                 products table, the intercept and variant rows on the VALU.  The parts they are differences FROM are exact: the null model's
-//                 block (null_h, a0) and, for the variant's row, the carrier sums of k_glm_bitdot.
+//                 block (null_h, a0) and, for the variant's row, the carrier sums of shk_bitdot_i8.
 //   k_glm_finish  fp64: assemble and factor the information matrix, bse, the exact Newton step (certificate: <= 5e-7, else the variant is
 //                 restarted by k_glm_slow), decisions and the output row.
 #ifndef GLM_LL_BLOCKS
@@ -1796,10 +1558,10 @@ static hipError_t launch_glm(hipStream_t st, int which, const uint64_t *T, int64
             const dim3 g256((unsigned)(Vpad / 256)), b256(256);
             hipLaunchKernelGGL((k_glm_fast<Q, true>), g256, b256, 0, st, T, Vpad, V, y, W, Wf, y1, y0, yc, P, wk, out, flags, flist, fcount);
             int r0 = 0;
-            if (P.bd_tab) {                                          // carrier sums: the first Newton step needs no pass, the finishing rounds use them too
-                // int8 matrix cores (bitdot_i8.hip: up to 16 columns = GLM_MAXQ + 2); the nibble-table kernel if it ever refuses
-                if (!P.bd_i8 || shk_bitdot_i8(st, T, Vpad, P.NB64, Q + 2, P.bd_i8, P.bd_scale, P.ch_bd) != hipSuccess)
-                    hipLaunchKernelGGL(k_glm_bitdot<Q>, g256, b256, 0, st, T, Vpad, P);
+            if (P.bd_i8) {                                           // carrier sums: the first Newton step needs no pass, the finishing rounds use them too
+                // int8 matrix cores (bitdot_i8.hip: up to 16 columns = GLM_MAXQ + 2)
+                const hipError_t e = shk_bitdot_i8(st, T, Vpad, P.NB64, Q + 2, P.bd_i8, P.bd_scale, P.ch_bd);
+                if (e != hipSuccess) return e;
                 if (P.b1 && n32 > 1) hipLaunchKernelGGL(k_glm_first_step<Q>, g256, b256, 0, st, Vpad, P, wk, P.ch_list[0], P.ch_cnt, P.ch_list[1], P.ch_cnt + 1);
                 else hipLaunchKernelGGL((k_glm_solve32<Q, true>), g256, b256, 0, st, Vpad, P, wk, P.ch_list[0], P.ch_cnt, P.ch_list[1], P.ch_cnt + 1,
                                         P.ch_list[2], cc, n32 == 1 ? 1 : 0);
@@ -1878,10 +1640,4 @@ extern "C" hipError_t shk_glm_launch(hipStream_t st, int Q, int which, const uin
     default: return hipErrorInvalidValue;
     }
 #undef GLM_CASE
-}
-
-extern "C" hipError_t shk_bitdot_build_tab(hipStream_t st, const double *vals, int NE, int N, int NB64, double *tab)
-{
-    hipLaunchKernelGGL(k_bitdot_build_tab, dim3((unsigned)NB64), dim3(256), 0, st, vals, NE, N, NB64, tab);
-    return hipGetLastError();
 }

@@ -43,7 +43,7 @@ struct GlmParams {
     // Workspaces are SoA over the batch's padded variant count: ch_bs / ch_g [PC][Vpad], ch_fac [PC(PC+1)/2][Vpad] (floats in the first half of a double array: the LDL^T factor of the single-precision Hessian), ch_hf the same
     // shape in float, ch_md / ch_rho [Vpad]; ch_list: two ping-pong lists for the Newton rounds, two for the chord rounds; ch_cnt their counters.
     // ch_list[4] + ch_cnt[30]: the converged variants, for the finishing kernels (fin_rounds; k_glm_ll / k_glm_dpass / k_glm_finish).
-    // bd_tab: nibble tables of (w0, w0 z, r0) at the null model (k_glm_bitdot -> ch_bd [Q+2][Vpad]); null_h = (sum w0, sum w0 z_j),
+    // bd_i8: the table of (w0, w0 z, r0) at the null model (shk_bitdot_i8 -> ch_bd [Q+2][Vpad]); null_h = (sum w0, sum w0 z_j),
     // null_g = the null model's score (sum r0, sum r0 z_j; ~1e-12), both in the standardised coordinates.
     int chord_on, chord_n32, chord_rounds, fin_rounds;
     // ll_first (round 3): the FIRST chord round's pass is the exact fp64 likelihood pass (k_glm_ll: ll, separation callback, score) instead of
@@ -55,8 +55,7 @@ struct GlmParams {
     double *ch_bs, *ch_fac, *ch_g, *ch_md, *ch_bd, *ch_ll;
     float *ch_hf, *ch_rho;
     int *ch_list[6], *ch_cnt;
-    const double *bd_tab;
-    const void *bd_i8; const double *bd_scale;   // bitdot_i8.hip: the same sums on the int8 matrix cores (digit table, column scales); null = k_glm_bitdot
+    const void *bd_i8; const double *bd_scale;   // bitdot_i8.hip: the carrier sums on the int8 matrix cores (digit table, column scales); null = no carrier sums (the first Newton step by a sample pass, k_glm_final)
     const float *wfp, *yf, *w0f;  // packed-fp32 passes (pass32_pk): wfp = per pair of samples a record of Q + 2 float2 (standardised covariates, y, w0;
                                   // each (even sample, odd sample)); yf, w0f = y and w0 as float arrays (the odd last sample); null = unpacked passes
     const double *rec;            // per sample a record of Q + 1 doubles (standardised covariates, then y): k_glm_score / k_glm_ll
@@ -76,7 +75,6 @@ struct GlmParams {
     // standardised covariates, s = 1 - 2 y, live = 1 (0 behind sample N), w0 = the null model's weight, as doubles (FFC<Q>::RS per sample).  null = the two-pass rounds.
     const void *ff_tab;
     const double *ff_rec;
-    const float *ff_rec32;        // the same records in single precision (same slots, half filled): the first pass
     const double *ff_inull;       // sum_i w0_i m2(i) over the degree-2 table's rows, with the table's own (hi + lo) values: the null model's covariate block of I
 };
 #define FIRTH_F_NOISE 8.9e-16      /* default of GlmParams.firth_noise: four ulp of F */

@@ -11,8 +11,8 @@
 //   chord=0          [1]  logistic: fp64-score Newton passes instead of the chord rounds (the form a run without covariates takes)
 //   chord_n32=K      [5]  single-precision Newton rounds before the chord rounds (1..8); stragglers restart in fp64
 //   chord_enter=X    [5e-3] step below which a variant enters the chord rounds
-//   bitdot=0         [1]  first Newton step by a sample pass, k_glm_final instead of the finishing kernels;  2: carrier sums by the nibble-table
-//                    kernel on the vector ALU (k_glm_bitdot) instead of the int8 matrix cores (bitdot_i8.hip)
+//   bitdot=0         [1]  first Newton step by a sample pass, k_glm_final instead of the finishing kernels (no carrier sums, bitdot_i8.hip);
+//                    2 is refused at set-up (sh_glm_setup)
 //   first_bordered=0 [1]  first Newton step through the general (Q+2)^2 solve
 //   pk=0             [1]  the passes without the packed single-precision records
 //   warm=0           [1]  no null-model warm start (the reference's start vector)
@@ -29,7 +29,6 @@
 //   firth_literal=1  [0]  Firth step halving by the reference's literal F(new) > F(old) on the rounds' own evaluation order
 //   firth_strict=1   [0]  literal rule + the reference's start vector + one log per sample (the A/B closest to the reference's own order)
 //   firth_fast=0     [1]  forced Firth at N >= 4096 through the exact two-pass rounds instead of the one-pass kernel (firth_fast.hip)
-//   firth_w=0        [1]  the one-pass kernel's single-precision first pass at one wavefront per SIMD (firth_fast.hip) instead of two (firth_fast_w.hip)
 //   lmm_limbs=L      [auto] int8 limbs of the LMM contraction;  lmm_tol=X [1e-8] bound above which a variant is contracted with the extra limbs
 //   qf=V             [4]  LMM contraction kernel: 0 = k_lmm_quadform_i8 (two wavefronts per SIMD), 3x = timing ablations
 //   ragged=0         [1]  LMM: the rows behind the last full 128-row tile contracted by the wide kernel itself (a narrow or a full segment) instead of
@@ -63,7 +62,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "firth_w", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

@@ -59,7 +59,7 @@ def test_forced_firth_calls_repeat_bit_for_bit(N, q, V, monkeypatch):
     e0 = np.zeros((0, 0))
     nl = fit_null(y, W, e0, False).llf; nf = fit_null(y, W, e0, False, firth=True)
     bits = pack_variants(K)
-    for route in (None, "firth_w=0", "firth_first32=0", "firth_first32=1"):
+    for route in (None, "firth_first32=0", "firth_first32=1"):
         if route is None:
             monkeypatch.delenv("SEERHIP_ROUTE", raising=False)
         else:

@@ -673,7 +673,6 @@ def test_logistic_fit_paths_agree(N, q, monkeypatch):
               dict(chord_enter="5e-2"),                              # early hand-over: several chord rounds per variant
               dict(chord_n32="2"),                                   # stragglers of the Newton rounds restarted in fp64 (workgroup kernel)
               dict(bitdot="0"),                                      # first step by a pass, k_glm_final instead of the finishing kernels
-              dict(bitdot="2"),                                      # carrier sums by round 3's nibble-table kernel (product: int8 matrix cores)
               dict(fin_rounds="0"), dict(pk="0"), dict(warm="0"), dict(newton="1"),
               dict(ll_first="0"),                                    # score pass first, likelihood pass last (one more fp64 pass per variant)
               dict(ll_first="0", chord_enter="5e-2"),
@@ -686,6 +685,14 @@ def test_logistic_fit_paths_agree(N, q, monkeypatch):
         for f in ("pvalue", "kbeta", "bse", "intercept"):
             close(r[f][~firth], base[f][~firth], rtol=5e-7 if f == "bse" else 2e-8, atol=1e-12, what="%s under %s" % (f, env))
         close(r["betas"][~firth], base["betas"][~firth], rtol=2e-8, atol=1e-10, what="betas under %s" % env)
+    # (bitdot=2 was round 3's nibble-table kernel for the carrier sums: a value the set-up refuses)
+    from pyseer_amd import _abi
+    monkeypatch.setenv("SEERHIP_ROUTE", "bitdot=2")
+    e = Engine(N)
+    with pytest.raises(_abi.SeerHipError, match="bitdot=2"):
+        e.glm_setup(y, W, False, nl, nf)
+    e.close()
+    monkeypatch.delenv("SEERHIP_ROUTE")
 
 
 @pytest.mark.parametrize("N,q,V,seed", [(1000, 10, 30000, 1), (5000, 10, 6000, 2)])
@@ -745,11 +752,11 @@ def test_one_pass_firth_equals_the_two_pass_rounds(N, q, V, monkeypatch):
     bits = pack_variants(K)
     out = {}
     # two: the exact rounds;  one: the one-pass kernels, their single-precision first pass at two wavefronts per SIMD (firth_fast_w.hip: 16-row
-    # tiles, 16 variants per wavefront, sums handed to a per-fit kernel);  one_w0: that pass at one wavefront per SIMD (firth_fast.hip, round 4)
+    # tiles, 16 variants per wavefront, sums handed to a per-fit kernel)
     # one_f64: every pass of the one-pass kernel in fp64, the first included (route key firth_first32)
     # one_r5: round 5's sequence -- ONE single-precision pass, then two fp64 passes (since round 6 the default is two single-precision passes at
     # two wavefronts per SIMD and ONE fp64 pass, which finishes the fit: its last step is ~1e-8)
-    for mode, route in (("two", "firth_fast=0"), ("one", None), ("one_w0", "firth_w=0"), ("one_f64", "firth_first32=0"), ("one_r5", "firth_first32=1")):
+    for mode, route in (("two", "firth_fast=0"), ("one", None), ("one_f64", "firth_first32=0"), ("one_r5", "firth_first32=1")):
         if route is None:
             monkeypatch.delenv("SEERHIP_ROUTE", raising=False)
         else:
@@ -759,7 +766,7 @@ def test_one_pass_firth_equals_the_two_pass_rounds(N, q, V, monkeypatch):
     a = out["two"]
     ok = np.isfinite(a["kbeta"])
     assert ok.sum() > V // 2
-    for mode in ("one", "one_w0", "one_f64", "one_r5"):
+    for mode in ("one", "one_f64", "one_r5"):
         b = out[mode]
         # (bit 18, SH_FLAG_FIRTH_SENSITIVE, is informational: "the stop rule was met within 1e-8 of its limit" may fall either way between two
         # arithmetic orders -- at most a couple of rows; every other bit is held exactly)

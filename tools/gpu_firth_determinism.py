@@ -9,7 +9,7 @@ from pyseer_amd.model import fit_null
 
 REP = int(os.environ.get("REP", 40))
 SHAPES = [(4100, 1, 1024), (4099, 3, 777), (5000, 10, 8192), (6007, 7, 1500), (4096, 10, 640), (8200, 5, 512), (4100, 2, 1024)]
-ROUTES = [("two", "firth_fast=0"), ("one", None), ("one_w0", "firth_w=0"), ("one_f64", "firth_first32=0"), ("one_r5", "firth_first32=1")]
+ROUTES = [("two", "firth_fast=0"), ("one", None), ("one_f64", "firth_first32=0"), ("one_r5", "firth_first32=1")]
 stop = False
 
 
