@@ -345,7 +345,32 @@ sh_job *sh_job_open(sh_ctx *ctx, int lmm, int print_filtered);
 void    sh_job_close(sh_job *job);
 int     sh_job_submit(sh_job *job, const uint8_t *bits, int64_t row_bytes, int64_t V, const int32_t *counts,
                       const char *names, const int64_t *name_off, int rows_are_dma);
+/* sh_job_submit_calls (round 20): a block of CALLS as the native VCF / Rtab readers deliver them (sh_vcf_next, sh_burden_fold, sh_rtab_next) -- per record
+ * the packed `present` and `missing` planes (row_bytes each), their popcounts and the reader's skip reason -- instead of rows that hold no missing call.
+ * Lifetime and depth rules of sh_job_submit: everything pointed at stays valid until the block has been collected.  Per row, after the batch's own
+ * fan-out (k_job_calls_mark):
+ *   skip != 0                      counted as pre-filtered, never a row of the output (not with print_filtered either), no pattern;
+ *   af = (n_present + n_missing) / n_samples outside the context's AF window (sh_set_af_filter, inclusive), or n_missing / n_samples > max_missing
+ *                                  af-filter, pre-filtered, every statistic NaN (af itself is printed);
+ *   n_missing == 0                 fitted from `present`, exactly as a row of sh_job_submit;
+ *   n_missing > 0                  pre_filtering (pyseer/model.py:31-70) over the samples that have a call; `pre-filtering-failed` where it fails or is
+ *                                  not finite, else filtered with `missing-data-error` (fixed effects, model.py:371-377) or `lrt-filtering-failed` (LMM,
+ *                                  lmm.py:190-204); every statistic but filter-pvalue NaN, lineage NA.
+ * Patterns (sh_job_set_patterns, sh_job_set_pattern_count): a row with a missing call is hashed as the float64 vector with NaN that the reference
+ * hashes (k_job_md5_calls) and enters the pattern set as that digest.  sh_job_set_samples: the carriers are present | missing.  The LMM's per-block
+ * lineage (sh_job_set_lineage, per_variant = 0) is none where the block's last record was skipped or holds a missing call. */
+int     sh_job_submit_calls(sh_job *job, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t V, const int32_t *n_present,
+                            const int32_t *n_missing, const int32_t *skip, const char *names, const int64_t *name_off, double max_missing);
 int     sh_job_collect(sh_job *job, const char **text, int64_t *nbytes, int64_t *counters);
+/* the records the text of the block last collected was formatted from, as the device compacted them: idx[r] = the row's index in its block,
+ * flags[r], cols[a * stride + r] = statistic a (filter-pvalue, lrt-pvalue, beta, beta-std-err, intercept / variant_h2, then the covariate
+ * slopes; NaN-masked as printed), r < nsel.  Valid until the next sh_job_submit / sh_job_submit_calls. */
+int     sh_job_records(sh_job *job, int64_t *nsel, const int32_t **idx, const uint32_t **flags, const double **cols, int64_t *stride, int *nrow);
+/* measurement (tools/calls_job_bench.py): stream events around k_job_calls_mark and, in a job that counts patterns without writing them, k_job_md5_calls
+ * of every later call block; sh_job_calls_times waits for them and returns their sums in ms and their numbers, and starts the record again.
+ * Both with no block in flight. */
+int     sh_job_set_calls_timing(sh_job *job, int on);
+int     sh_job_calls_times(sh_job *job, double *mark_ms, int64_t *mark_launches, double *md5_ms, int64_t *md5_launches);
 int64_t sh_job_pending(sh_job *job);
 int     sh_job_depth(sh_job *job);     /* blocks that may be submitted and not yet collected: 3 (LMM), 2 + lanes (fixed effects) */
 int     sh_job_set_lineage(sh_job *job, const char *const *labels, int n_labels, int per_variant);

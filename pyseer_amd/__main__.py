@@ -16,7 +16,8 @@ has the members of a BGZF file decoded on the device too (k_bgzf_inflate); for a
 
 VCF is read as text (plain, gzip or BGZF; no index, no pysam): natively with the sample columns tokenised on the device, or by the Python
 reader (--python-reader).  An Rtab (--pres) goes the same two ways: framed natively with its calls tokenised on the device (k_rtab_pack), or
-line by line (--python-reader; also with --gpus, and for a header that names a sample twice).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
+line by line (--python-reader; also with --gpus, and for a header that names a sample twice).  --device-calls sends the blocks of both native readers to the job
+stream as parsed (sh_job_submit_calls: the filters, the rows with missing calls and their patterns on the device, no Python per variant; same bytes out).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
 and --pres and --python-reader line by line.  BCF 2.1 / 2.2 is read through --vcf wherever VCF text is (sniffed from the decoded bytes, whatever the file is called): natively with each
 record's GT vector reduced on the device (k_bcf_gt_pack), or by the Python reader (--python-reader, input.BcfFile).
 Not supported (out of scope): --wg rf / blup, --gpus / the packed cache with a VCF or BCF, and around BCF: .csi / .tbi indexes (burden
@@ -190,6 +191,10 @@ def get_options(argv=None):
     ot.add_argument('--device-inflate', action='store_true', default=False,
                     help='Decode the members of a BGZF (bgzip) --kmers file on the device as well; implies --device-reader and is ignored where '
                          'that is ignored; for any other container it is --device-reader')
+    ot.add_argument('--device-calls', action='store_true', default=False,
+                    help='Send the blocks of the native VCF / BCF reader (also with --burden) and of the native Rtab reader to the job stream as '
+                         'parsed: the filters, the rows with missing calls and their patterns are handled on the device, and no Python runs per '
+                         'variant; same output. Ignored with --python-reader, --python-sink, --serial-sink and --gpus')
     ot.add_argument('--python-sink', action='store_true', default=False,
                     help='Format every output row in Python (one result tuple per variant) instead of the native block sink')
     ot.add_argument('--serial-sink', action='store_true', default=False,
@@ -241,7 +246,7 @@ def main(argv=None):
         sys.stderr.write("h^2 = " + '{0:.2f}'.format(h2) + "\n")
         lmm_fit = (lmm, h2)
     p = inp.p
-    state = model_state(options, inp, lmm_fit, (options.min_af, options.max_af) if (plan.native or options.load_packed) else None)
+    state = model_state(options, inp, lmm_fit, (options.min_af, options.max_af) if (plan.native or options.load_packed or plan.calls_job) else None)
     engs = []
     if not plan.proc_mode:
         # One context per listed device; the same device may be listed twice (two contexts on one GPU: the test of

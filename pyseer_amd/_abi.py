@@ -83,6 +83,11 @@ SIGNATURES = {
     "sh_job_open": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int]),
     "sh_job_close": (None, [C.c_void_p]),
     "sh_job_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "sh_job_submit_calls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]),
+    "sh_job_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_int)]),
+    "sh_job_set_calls_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "sh_job_calls_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "sh_job_collect": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sh_job_pending": (C.c_int64, [C.c_void_p]),
     "sh_job_depth": (C.c_int, [C.c_void_p]),

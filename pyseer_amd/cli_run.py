@@ -266,7 +266,7 @@ def setup_engine(engine, st, share_from=None):
 # ---- the plan ----------------------------------------------------------------------------------------------------------------------------------
 # The decisions of a run: devices (of --gpus; None without it: the single --gpu), proc_mode (one process per device), the readers, the route of the blocks
 RunPlan = collections.namedtuple("RunPlan", "devices proc_mode var_type native native_vcf native_rtab dev_inflate dev_reader "
-                                 "job_path lmm_block_lineage job_block job_ahead want_pat cache_selected packed_c_loop")
+                                 "job_path lmm_block_lineage job_block job_ahead want_pat cache_selected packed_c_loop calls_job")
 
 
 def make_plan(options, route, stdout_fd, patterns_fd=True, cache_selected=False, lanes=None, proc_mode=None):
@@ -294,12 +294,19 @@ def make_plan(options, route, stdout_fd, patterns_fd=True, cache_selected=False,
     # run inside the stream too: sh_job_set_lineage / _patterns / _samples) a block goes to the library as parsed and comes back as the text of its printed rows: the AF
     # window, the NaN masks, the counters and the choice of rows run on the device, the host formats printed rows only.  Output without
     # --print-filtered does not depend on where blocks end, so short blocks are coalesced (a 3000-row block is 90 us of GPU time).
-    job_path = bool((native or options.load_packed) and not options.python_sink and not options.serial_sink and route("job", "1") != "0")
+    # --device-calls (SEERHIP_ROUTE calls_job=1; round 20): the native VCF reader's blocks (text, BCF, burden regions) and the native Rtab reader's go to the
+    # job stream as parsed -- planes with missing calls, counts, skip reasons (sh_job_submit_calls) -- instead of through _vcf_packed_block and the
+    # sinks of the Python block loop.  An option: the default route of these inputs is what it was.
+    native_vcf = bool(var_type == "vcf" and reader)
+    calls_job = bool((native_vcf or native_rtab) and (options.device_calls or route("calls_job", "0") == "1") and options.gpus is None)
+    job_path = bool((native or options.load_packed or calls_job) and not options.python_sink and not options.serial_sink and route("job", "1") != "0")
+    calls_job = calls_job and job_path
     # (--lineage, round 6: fit_lineage_effect runs inside the stream, for printed rows -- sh_job_set_lineage.  The LMM's lineage is that of each
     # block's LAST variant (pyseer/lmm.py:209-213, the stale `k`), so its blocks must end where the reference's do: no coalescing)
     lmm_block_lineage = bool(options.lineage and options.lmm and not options.lmm_lineage_per_variant)
     # (2^18 rows: a call of 2^16 runs the LMM 7 % slower, the logistic path 27 %, Firth 15 % -- profiles/r06/rows_per_call.txt; round 5 had 2^16)
-    job_block = options.block_size if (options.print_filtered or lmm_block_lineage or not job_path) else max(options.block_size, 1 << 18)
+    # (call blocks are read whole before they are submitted, two planes each, and several are in flight: 2^14 rows -- 21 MB at N = 5000)
+    job_block = options.block_size if (options.print_filtered or lmm_block_lineage or not job_path) else max(options.block_size, 1 << (14 if calls_job else 18))
     # the reader runs as far ahead as the job stream holds blocks in flight (fixed effects: 2 + lanes, include/seerhip.h sh_job_depth)
     job_ahead = (2 + lanes) if (job_path and not options.lmm and lanes is not None) else 2
     # --count-patterns: the set of distinct patterns on the first (the only) device.  The job stream inserts every tested row there itself
@@ -310,8 +317,8 @@ def make_plan(options, route, stdout_fd, patterns_fd=True, cache_selected=False,
     # Python, as round 5 had it and as text input still has it)
     # (the library's loop takes a cache of the run's own samples only: a selected cache goes through the Python loop)
     packed_c_loop = bool(job_path and options.load_packed and not cache_selected and route("job", "1") != "py" and stdout_fd and patterns_fd)
-    return RunPlan(devices, proc_mode, var_type, native, var_type == "vcf" and reader, native_rtab, dev_inflate, dev_reader,
-                   job_path, lmm_block_lineage, job_block, job_ahead, want_pat, bool(cache_selected), packed_c_loop)
+    return RunPlan(devices, proc_mode, var_type, native, native_vcf, native_rtab, dev_inflate, dev_reader,
+                   job_path, lmm_block_lineage, job_block, job_ahead, want_pat, bool(cache_selected), packed_c_loop, calls_job)
 
 
 # ---- the run's context and its input -----------------------------------------------------------------------------------------------------------
@@ -376,6 +383,15 @@ def open_blocks(ctx, src, cache_stamp=None, part=None, eng=None):
             src.cache_out = I.PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
         return I.iter_packed_blocks_native(p, src.var_file, *af, plan.job_block, want_patterns=plan.want_pat, want_samples=options.print_samples, save_to=src.cache_out,
                                            raw=plan.job_path, engine=(engs[0] if (plan.dev_reader and engs) else None), inflate=(True if options.device_inflate else None))
+    if plan.calls_job and plan.native_vcf:
+        # (the reader and the job stream share the first context: the blocks are read on the thread that submits them, between its calls)
+        return I.iter_job_call_blocks_vcf(p, src.var_file, engs[0], plan.job_block, burden_regions=(list(src.burden_regions) if options.burden else None))
+    if plan.calls_job:
+        try:
+            return I.iter_job_call_blocks_rtab(I.NativeRtabReader(src.var_file, [str(x) for x in p.index], engs[0], plan.job_block))
+        except I.RtabDuplicateSample:
+            # a header that names a sample twice is read line by line (iter_packed_blocks_rtab_native), through the Python block loop
+            ctx.plan = plan = plan._replace(calls_job=False, job_path=False, job_block=options.block_size, want_pat=bool(options.output_patterns or options.count_patterns))
     if plan.native_vcf:
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
         return I.iter_packed_blocks_vcf_native(p, src.var_file, engs[0], *af, options.max_missing, options.block_size,
@@ -402,7 +418,7 @@ def new_tm():
 
 
 def run_stream_job(ctx, engs, blocks, write_text, tm, stop=None, write_patterns=None):
-    """One stream of RawBlocks through the library's job stream, block k on context k % len(engs) (each context pipelined Job.depth deep: the rows of its next block cross
+    """One stream of RawBlocks (or, --device-calls, CallBlocks) through the library's job stream, block k on context k % len(engs) (each context pipelined Job.depth deep: the rows of its next block cross
     PCIe while the block before runs its kernels and the one before that is written out here). Returns (pre-filtered, tested, printed)."""
     jobs = [make_job(ctx, e_, write_patterns is not None) for e_ in engs]
     n = Counts()
@@ -435,7 +451,10 @@ def run_stream_job(ctx, engs, blocks, write_text, tm, stop=None, write_patterns=
             while jb.pending() >= jb.depth:
                 take()
             t_e = time.perf_counter()
-            jb.submit(rb.bits, rb.counts, rb.blob, rb.off, rows_are_dma=rb.dma, keep=rb.release)
+            if getattr(rb, "missing", None) is not None:  # a CallBlock of the native VCF / Rtab reader (input.iter_job_call_blocks_*)
+                jb.submit_calls(rb.present, rb.missing, rb.n_present, rb.n_missing, rb.skip, rb.blob, rb.off, ctx.options.max_missing)
+            else:
+                jb.submit(rb.bits, rb.counts, rb.blob, rb.off, rows_are_dma=rb.dma, keep=rb.release)
             tm["engine"] += time.perf_counter() - t_e; tm["blocks"] += 1
             order.append(jb)
             # depth - 1 blocks stay in flight per context (one uploading, one computing per lane); the next is collected, formatted and written

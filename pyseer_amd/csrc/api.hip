@@ -64,11 +64,16 @@ int64_t sh_format_records(const char *, const int64_t *, const int32_t *, int, c
 // (writer.cpp: sh_format_records + the two sample lists of --print-samples from the printed rows' host bits)
 int64_t format_records_samples(const char *, const int64_t *, const int32_t *, int, const int32_t *, int64_t, const double *const *, int, const double *, int64_t, int,
                                const uint8_t *, const int32_t *, const char *const *, int, const uint32_t *, const char **, const uint8_t *, int64_t, const char *,
-                               const int64_t *, const int32_t *);
-hipError_t shk_job_patterns(hipStream_t, const uint64_t *, int64_t, int64_t, int, const uint32_t *, int *, long long *, uint32_t *, char *, char *);
+                               const int64_t *, const int32_t *, const uint8_t *);
+hipError_t shk_job_patterns(hipStream_t, const uint64_t *, int64_t, int64_t, int, const uint32_t *, int *, long long *, uint32_t *, char *, char *, const uint8_t *,
+                            const uint8_t *, int64_t, const int32_t *);
+hipError_t shk_job_calls_mark(hipStream_t, const uint8_t *, const uint8_t *, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, const uint64_t *,
+                              const uint64_t *, const double *, int, int, int, int, double, double, double, double, double *, uint32_t *, uint32_t *);
+hipError_t shk_job_md5_calls(hipStream_t, const uint8_t *, const uint8_t *, int64_t, int64_t, int, const uint32_t *, const int32_t *, uint32_t *);
 // patset_kernels.hip
 hipError_t shk_ps_insert_rows(hipStream_t, const uint8_t *, int64_t, int64_t, int, const uint32_t *, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
 hipError_t shk_ps_insert_keys(hipStream_t, const uint64_t *, int64_t, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
+hipError_t shk_ps_insert_digests(hipStream_t, const uint32_t *, int64_t, const uint32_t *, const int32_t *, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
 hipError_t shk_ps_rehash(hipStream_t, const unsigned long long *, const unsigned long long *, int64_t, unsigned long long *, unsigned long long *, int64_t, unsigned long long *);
 #define JOB_ROWS_PER_BLOCK_HOST 1024
 // enet_kernels.hip

@@ -86,7 +86,8 @@ struct LinList { const int *list; const long long *cnt; const uint32_t *flags; i
 __host__ __device__ inline bool lin_wanted(uint32_t f, int mode)
 {
     if (f & SH_FLAG_PREFILTER) return false;
-    return mode == 2 ? (f & SH_FLAG_FILTER) == 0 : (f & SH_NOTE_FIRTH_FAIL) == 0;
+    // (missing-data-error: a row of a call block with a missing call -- model.py:371-377 returns before fit_lineage_effect, as for firth-fail)
+    return mode == 2 ? (f & SH_FLAG_FILTER) == 0 : (f & (SH_NOTE_FIRTH_FAIL | SH_NOTE_MISSING_DATA)) == 0;
 }
 #define LIN_COUNTS_MAX 1023        /* most cluster columns of the count route (k_glm_lineage_counts, glm_lineage.hip): 52 bytes of LDS per column */
 

@@ -25,6 +25,11 @@ struct JobSlot {
     hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
     // the block in the slot
     const uint8_t *bits = nullptr; int64_t row_bytes = 0, V = 0; const int32_t *counts = nullptr; const char *names = nullptr; const int64_t *name_off = nullptr;
+    // a call block (sh_job_submit_calls): d_bits holds [present | missing | n_present, n_missing, skip] (calls_layout), miss: the caller's missing plane
+    // (--print-samples), cnt_host: present + missing per row (the printed af), no_last_lineage: the block's last row was skipped or holds a missing call
+    int calls = 0, no_last_lineage = 0; const uint8_t *miss = nullptr; double max_missing = 0.0; std::vector<int32_t> cnt_host;
+    uint32_t *d_flags_rows = nullptr; int64_t cap_frows = 0;            // --count-patterns: the flags by which the pattern set takes packed rows
+    int64_t cap_dig = 0;
     int state = 0;                                                      // 0 free, 1 rows on their way, 2 kernels queued, 3 the lane that ran them failed
     int rc = 0; std::string err;                                        // (state 3)
 };
@@ -51,7 +56,24 @@ struct sh_job {
     int pattern_count = 0;
     // --print-samples (sh_job_set_samples): the sample names in the order the reference lists them (sorted), for the printed rows' two lists
     std::string smp_blob; std::vector<int64_t> smp_off; std::vector<int32_t> smp_order;
+    // sh_job_set_calls_timing: stream events around k_job_calls_mark [0] and k_job_md5_calls [1] of every call block (recorded by whichever
+    // thread queues the block's kernels: under mu)
+    int time_calls = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> tev_calls[2];
 };
+
+// one kernel launch between two events on st, kept in j->tev_calls[which] (sh_job_calls_times)
+static int job_timed(sh_job *j, int which, hipStream_t st, const std::function<hipError_t()> &launch)
+{
+    if (!j->time_calls) { HIPCHK(launch()); return SH_OK; }
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+    HIPCHK(hipEventRecord(a, st));
+    const hipError_t e = launch();
+    HIPCHK(hipEventRecord(b, st));
+    { std::lock_guard<std::mutex> lk(j->mu); j->tev_calls[which].emplace_back(a, b); }
+    HIPCHK(e);
+    return SH_OK;
+}
 
 static long long *slot_hdr(JobSlot &s) { return (long long *)s.h_res; }
 static int32_t *slot_idx(JobSlot &s) { return (int32_t *)(s.h_res + 64); }
@@ -59,8 +81,17 @@ static uint32_t *slot_flags(JobSlot &s) { return (uint32_t *)(s.h_res + 64 + (si
 static double *slot_cols(JobSlot &s) { return (double *)(s.h_res + 64 + (size_t)s.cap_res_rows * 8); }
 static int32_t *slot_lin(JobSlot &s) { return (int32_t *)(s.h_res + 64 + (size_t)s.cap_res_rows * (8 + 8 * (size_t)s.res_nrow)); }
 
+// where the parts of a call block lie in the slot's device buffer (and in its pinned slab)
+struct CallsLayout { size_t miss, ints, total; };
+static CallsLayout calls_layout(int64_t V, int64_t row_bytes)
+{
+    CallsLayout L; L.miss = (size_t)(V * row_bytes); L.ints = (2 * L.miss + 15) / 16 * 16; L.total = L.ints + (size_t)V * 12;
+    return L;
+}
+
 static void job_free_slot(JobSlot &s)
 {
+    hipFree(s.d_flags_rows);
     hipFree(s.d_bits); hipFree(s.d_out); hipFree(s.d_flags); hipFree(s.d_bcount); hipFree(s.d_hdr); hipFree(s.d_sel); hipFree(s.d_T1); hipFree(s.d_dig); hipFree(s.d_pat);
     if (s.h_pat) hipHostFree(s.h_pat);
     if (s.hp_bits) hipHostFree(s.hp_bits);
@@ -70,10 +101,13 @@ static void job_free_slot(JobSlot &s)
     s = JobSlot();
 }
 
-static int job_ensure(sh_job *j, JobSlot &s, int64_t V, int64_t row_bytes, bool staged)
+static int job_ensure(sh_job *j, JobSlot &s, int64_t V, int64_t row_bytes, bool staged, bool calls = false)
 {
     const int nrow = j->nrow;
-    if (V * row_bytes > s.cap_bits) { hipFree(s.d_bits); s.d_bits = nullptr; s.cap_bits = 0; HIPCHK(hipMalloc((void **)&s.d_bits, V * row_bytes)); s.cap_bits = V * row_bytes; }
+    const int64_t nbits = calls ? (int64_t)calls_layout(V, row_bytes).total : V * row_bytes;
+    if (nbits > s.cap_bits) { hipFree(s.d_bits); s.d_bits = nullptr; s.cap_bits = 0; HIPCHK(hipMalloc((void **)&s.d_bits, nbits)); s.cap_bits = nbits; }
+    if (calls && j->pattern_count && V > s.cap_frows) { hipFree(s.d_flags_rows); s.d_flags_rows = nullptr; s.cap_frows = 0; HIPCHK(dmalloc(&s.d_flags_rows, V)); s.cap_frows = V; }
+    if ((j->patterns || (calls && j->pattern_count)) && V > s.cap_dig) { hipFree(s.d_dig); s.d_dig = nullptr; s.cap_dig = 0; HIPCHK(dmalloc(&s.d_dig, (size_t)V * 4)); s.cap_dig = V; }
     if (V > s.cap_rows || nrow > s.cap_nrow) {
         hipFree(s.d_out); hipFree(s.d_flags); hipFree(s.d_bcount); hipFree(s.d_hdr); s.d_out = nullptr; s.d_flags = nullptr; s.d_bcount = nullptr; s.d_hdr = nullptr; s.cap_rows = 0;
         const int64_t cv = std::max(V, s.cap_rows); const int cn = std::max(nrow, s.cap_nrow);
@@ -90,15 +124,15 @@ static int job_ensure(sh_job *j, JobSlot &s, int64_t V, int64_t row_bytes, bool 
     if (j->lin_mode == 1 && V > s.cap_sel) { hipFree(s.d_sel); s.d_sel = nullptr; s.cap_sel = 0; HIPCHK(dmalloc(&s.d_sel, V)); s.cap_sel = V; }
     if (j->lin_mode == 2 && !s.d_T1) HIPCHK(dmalloc(&s.d_T1, (size_t)256 * j->c->NB64p));
     if (j->patterns && V > s.cap_pat) {
-        hipFree(s.d_dig); hipFree(s.d_pat); if (s.h_pat) hipHostFree(s.h_pat);
-        s.d_dig = nullptr; s.d_pat = nullptr; s.h_pat = nullptr; s.cap_pat = 0;
-        HIPCHK(dmalloc(&s.d_dig, (size_t)V * 4)); HIPCHK(hipMalloc((void **)&s.d_pat, (size_t)V * 25));
+        hipFree(s.d_pat); if (s.h_pat) hipHostFree(s.h_pat);
+        s.d_pat = nullptr; s.h_pat = nullptr; s.cap_pat = 0;
+        HIPCHK(hipMalloc((void **)&s.d_pat, (size_t)V * 25));
         HIPCHK(hipHostMalloc((void **)&s.h_pat, (size_t)V * 25, hipHostMallocDefault)); s.cap_pat = V;
     }
-    if (staged && V * row_bytes > s.cap_hp) {
+    if (staged && nbits > s.cap_hp) {
         if (s.hp_bits) hipHostFree(s.hp_bits);
         s.hp_bits = nullptr; s.cap_hp = 0;
-        HIPCHK(hipHostMalloc((void **)&s.hp_bits, V * row_bytes, hipHostMallocDefault)); s.cap_hp = V * row_bytes;
+        HIPCHK(hipHostMalloc((void **)&s.hp_bits, nbits, hipHostMallocDefault)); s.cap_hp = nbits;
     }
     if (!s.ev_h2d) {
         HIPCHK(hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
@@ -132,11 +166,25 @@ static int job_compute_on(sh_job *j, JobSlot &s, sh_ctx *k)
     HIPCHK(hipStreamWaitEvent(k->stream, s.ev_h2d, 0));
     int rc = j->lmm ? sh_lmm_batch_dev(k, s.d_bits, s.row_bytes, s.V, s.d_out, s.d_flags) : sh_glm_batch_dev(k, s.d_bits, s.row_bytes, s.V, s.d_out, s.d_flags);
     if (rc) return rc;
+    const CallsLayout CL = calls_layout(s.V, s.row_bytes);
+    const uint8_t *d_miss = s.calls ? s.d_bits + CL.miss : nullptr;
+    const int32_t *d_np = s.calls ? (const int32_t *)(s.d_bits + CL.ints) : nullptr, *d_nm = s.calls ? d_np + s.V : nullptr, *d_skip = s.calls ? d_nm + s.V : nullptr;
+    if (s.calls) {
+        // skipped records, rows outside the filters and rows with missing calls, per submitted row (k_job_calls_mark, job_kernels.hip); the
+        // phenotype masks and the centred phenotype are those of the context that ran the batch
+        const bool lm = j->lmm != 0;
+        rc = job_timed(j, 0, k->stream, [&] {
+            return shk_job_calls_mark(k->stream, s.d_bits, d_miss, s.row_bytes, s.V, d_np, d_nm, d_skip, lm ? k->d_y1 : k->glm.d_y1, lm ? k->d_y0 : k->glm.d_y0,
+                                      lm ? k->d_yc : k->glm.d_yc, k->N, j->lmm, lm ? k->fin.continuous : k->glm.P.continuous, j->nrow, k->min_af, k->max_af,
+                                      s.max_missing, lm ? k->fin.pret : k->glm.P.pret, s.d_out, s.d_flags, j->pattern_count ? s.d_flags_rows : nullptr); });
+        if (rc) return rc;
+    }
     HIPCHK(shk_job_select(k->stream, s.d_flags, s.d_out, s.V, j->nrow, j->lmm, j->print_filtered, s.d_bcount, s.d_hdr, slot_hdr(s), slot_idx(s), slot_flags(s),
                           slot_cols(s), s.cap_res_rows, j->lin_mode == 1 ? s.d_sel : nullptr));
     if (j->pattern_count) {
         // the rows as submitted (the batch's own copy may be AF-compacted, de-duplicated or complemented), behind the flags they are chosen by
-        rc = patset_insert_rows(j->c, k->stream, s.d_bits, s.row_bytes, s.V, s.d_flags); if (rc) return rc;
+        // (a call block's rows with missing calls are no packed rows: they enter as md5 digests below)
+        rc = patset_insert_rows(j->c, k->stream, s.d_bits, s.row_bytes, s.V, s.calls ? s.d_flags_rows : s.d_flags); if (rc) return rc;
     }
     const int64_t Vpad = (s.V + 255) / 256 * 256;
     if (j->lin_mode == 1 || j->patterns) {
@@ -146,7 +194,12 @@ static int job_compute_on(sh_job *j, JobSlot &s, sh_ctx *k)
         HIPCHK(shk_repack_bits(k->stream, s.d_bits, s.row_bytes, s.V, Vpad, k->N, k->NB64p, k->d_T, nullptr));
     }
     if (j->patterns)
-        HIPCHK(shk_job_patterns(k->stream, k->d_T, Vpad, s.V, k->N, s.d_flags, s.d_bcount, s.d_hdr + 4, s.d_dig, s.d_pat, s.h_pat));
+        HIPCHK(shk_job_patterns(k->stream, k->d_T, Vpad, s.V, k->N, s.d_flags, s.d_bcount, s.d_hdr + 4, s.d_dig, s.d_pat, s.h_pat, s.d_bits, d_miss, s.row_bytes, d_nm));
+    else if (s.calls && j->pattern_count) {
+        rc = job_timed(j, 1, k->stream, [&] { return shk_job_md5_calls(k->stream, s.d_bits, d_miss, s.row_bytes, s.V, k->N, s.d_flags, d_nm, s.d_dig); });
+        if (rc) return rc;
+    }
+    if (s.calls && j->pattern_count) { rc = patset_insert_digests(j->c, k->stream, s.d_dig, s.V, s.d_flags, d_nm); if (rc) return rc; }
     if (j->lin_mode) {
         // fit_lineage_effect (model.py:151-199) on the device, for rows the run prints: the design [1, lineages, covariates] is the parent
         // context's (sh_lineage_setup)
@@ -205,6 +258,35 @@ sh_job *sh_job_open(sh_ctx *c, int lmm, int print_filtered)
     return j;
 }
 
+int sh_job_set_calls_timing(sh_job *j, int on)
+{
+    if (!j) return fail(SH_EINVAL, "null job");
+    if (j->n_submitted != j->n_collected) return fail(SH_EINVAL, "sh_job_set_calls_timing: blocks are in flight");
+    j->time_calls = on ? 1 : 0;
+    return SH_OK;
+}
+
+// the sum of the recorded launches so far (and their number), after waiting for them; the record starts again
+int sh_job_calls_times(sh_job *j, double *mark_ms, int64_t *mark_launches, double *md5_ms, int64_t *md5_launches)
+{
+    if (!j || !mark_ms || !mark_launches || !md5_ms || !md5_launches) return fail(SH_EINVAL, "sh_job_calls_times: null argument");
+    if (j->n_submitted != j->n_collected) return fail(SH_EINVAL, "sh_job_calls_times: blocks are in flight");
+    HIPCHK(hipSetDevice(j->c->device));
+    double ms[2] = {0.0, 0.0}; int64_t n[2] = {0, 0};
+    std::lock_guard<std::mutex> lk(j->mu);
+    for (int w = 0; w < 2; ++w) {
+        for (auto &pr : j->tev_calls[w]) {
+            float t = 0.0f;
+            HIPCHK(hipEventSynchronize(pr.second)); HIPCHK(hipEventElapsedTime(&t, pr.first, pr.second));
+            hipEventDestroy(pr.first); hipEventDestroy(pr.second);
+            ms[w] += (double)t; ++n[w];
+        }
+        j->tev_calls[w].clear();
+    }
+    *mark_ms = ms[0]; *mark_launches = n[0]; *md5_ms = ms[1]; *md5_launches = n[1];
+    return SH_OK;
+}
+
 int sh_job_set_patterns(sh_job *j, int on)
 {
     if (!j) return fail(SH_EINVAL, "null job");
@@ -259,6 +341,7 @@ void sh_job_close(sh_job *j)
     hipStreamSynchronize(j->c->stream);
     if (j->copy_stream) { hipStreamSynchronize(j->copy_stream); hipStreamDestroy(j->copy_stream); }
     for (auto &s : j->slot) job_free_slot(s);
+    for (auto &v : j->tev_calls) for (auto &pr : v) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     delete j;
 }
 
@@ -283,6 +366,7 @@ static int job_submit_rows(sh_job *j, const uint8_t *bits, const uint8_t *const 
     JobSlot &s = j->slot[j->n_submitted % j->depth];
     int rc = job_ensure(j, s, V, row_bytes, !rows_are_dma); if (rc) return rc;
     s.bits = bits; s.row_bytes = row_bytes; s.V = V; s.counts = counts; s.names = names; s.name_off = name_off;
+    s.calls = 0; s.miss = nullptr; s.no_last_lineage = 0;
     // rows -> device on the copy stream.  DMA-able where they lie (pinned or registered: the packed-cache mapping): nothing but the descriptor
     // is touched by the CPU.  Otherwise through this slot's pinned slab, filled by the caller and the idle workers of the process-wide pool.
     const uint8_t *src = bits;
@@ -324,6 +408,61 @@ int sh_job_submit(sh_job *j, const uint8_t *bits, int64_t row_bytes, int64_t V, 
 {
     if (!bits) return fail(SH_EINVAL, "sh_job_submit: bad argument");
     return job_submit_rows(j, bits, nullptr, nullptr, 0, row_bytes, V, counts, names, name_off, rows_are_dma);
+}
+
+// A block of calls as the native VCF / Rtab readers deliver them (round 20): the two packed planes, their counts and the reader's skip reason per
+// record.  Every row is fitted from `present` by the batch; k_job_calls_mark then restates, per submitted row, what the reference does with
+// skipped records, with rows outside the AF window (the context's: sh_set_af_filter) or above max_missing, and with rows that hold a missing
+// call.  The planes and the counts go through the slot's pinned slab in one upload.
+int sh_job_submit_calls(sh_job *j, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t V, const int32_t *n_present, const int32_t *n_missing,
+                        const int32_t *skip, const char *names, const int64_t *name_off, double max_missing)
+{
+    if (!j) return fail(SH_EINVAL, "null job");
+    if (!present || !missing || !n_present || !n_missing || !skip || !names || !name_off || V <= 0 || row_bytes <= 0) return fail(SH_EINVAL, "sh_job_submit_calls: bad argument");
+    if (row_bytes * 8 < j->c->N) return fail(SH_ESHAPE, "row_bytes*8 < n_samples: shape mismatch between snps and Y");
+    if (j->n_submitted - j->n_collected >= (uint64_t)j->depth) return fail(SH_EINVAL, "sh_job_submit_calls: every slot holds a block; collect one first");
+    for (int64_t v = 0; v < V; ++v)
+        if (n_present[v] < 0 || n_missing[v] < 0 || (int64_t)n_present[v] + n_missing[v] > (int64_t)row_bytes * 8) return fail(SH_EINVAL, "sh_job_submit_calls: impossible counts");
+    sh_ctx *c = j->c;
+    HIPCHK(hipSetDevice(c->device));
+    JobSlot &s = j->slot[j->n_submitted % j->depth];
+    int rc = job_ensure(j, s, V, row_bytes, true, true); if (rc) return rc;
+    s.bits = present; s.miss = missing; s.row_bytes = row_bytes; s.V = V; s.names = names; s.name_off = name_off;
+    s.calls = 1; s.max_missing = max_missing; s.no_last_lineage = (skip[V - 1] != 0 || n_missing[V - 1] != 0) ? 1 : 0;
+    s.cnt_host.resize((size_t)V);
+    for (int64_t v = 0; v < V; ++v) s.cnt_host[(size_t)v] = n_present[v] + n_missing[v];   // the printed af: (present + missing) / N (input.py:446)
+    s.counts = s.cnt_host.data();
+    const CallsLayout CL = calls_layout(V, row_bytes);
+    {
+        shost::CpuScope cs(shost::ST_STAGE_COPY);
+        std::memcpy(s.hp_bits, present, CL.miss); std::memcpy(s.hp_bits + CL.miss, missing, CL.miss);
+        if (CL.ints > 2 * CL.miss) std::memset(s.hp_bits + 2 * CL.miss, 0, CL.ints - 2 * CL.miss);
+        int32_t *ints = (int32_t *)(s.hp_bits + CL.ints);
+        std::memcpy(ints, n_present, (size_t)V * 4); std::memcpy(ints + V, n_missing, (size_t)V * 4); std::memcpy(ints + 2 * V, skip, (size_t)V * 4);
+    }
+    {
+        shost::CpuScope cs(shost::ST_SUBMIT);
+        HIPCHK(hipMemcpyAsync(s.d_bits, s.hp_bits, CL.total, hipMemcpyHostToDevice, j->copy_stream));
+        HIPCHK(hipEventRecord(s.ev_h2d, j->copy_stream));
+    }
+    s.state = 1;
+    ++j->n_submitted;
+    while (j->n_computed + (j->lanes > 1 ? 0 : 1) < j->n_submitted) {    // (as sh_job_submit hands the blocks' kernels over)
+        rc = job_compute(j, j->slot[j->n_computed % j->depth]); if (rc) return rc;
+        ++j->n_computed;
+    }
+    return SH_OK;
+}
+
+// the compacted records of the block last collected, as the device left them (what the text was formatted from): for callers that want the
+// numbers and the flags of the printed rows, not their text.  Valid until the next submit.
+int sh_job_records(sh_job *j, int64_t *nsel, const int32_t **idx, const uint32_t **flags, const double **cols, int64_t *stride, int *nrow)
+{
+    if (!j || !nsel || !idx || !flags || !cols || !stride || !nrow) return fail(SH_EINVAL, "sh_job_records: null argument");
+    if (j->n_collected == 0) return fail(SH_EINVAL, "sh_job_records: nothing collected");
+    JobSlot &s = j->slot[(j->n_collected - 1) % j->depth];
+    *nsel = slot_hdr(s)[0]; *idx = slot_idx(s); *flags = slot_flags(s); *cols = slot_cols(s); *stride = s.cap_res_rows; *nrow = j->nrow;
+    return SH_OK;
 }
 
 int64_t sh_job_pending(sh_job *j) { return j ? (int64_t)(j->n_submitted - j->n_collected) : 0; }
@@ -370,7 +509,8 @@ int sh_job_collect(sh_job *j, const char **text, int64_t *nbytes, int64_t *count
         const int32_t *lin = nullptr;
         if (j->lin_mode == 1) lin = slot_lin(s);
         else if (j->lin_mode == 2) {                                    // the block's one fit, for the rows that passed (lmm.py:200-213)
-            const int32_t ml = *(const int32_t *)(slot_hdr(s) + 4);
+            // (a call block whose last variant was skipped or holds a missing call has no lineage: cli_run.last_variant_lineage)
+            const int32_t ml = s.no_last_lineage ? -1 : *(const int32_t *)(slot_hdr(s) + 4);
             const uint32_t *fl = slot_flags(s);
             j->lin_host.resize((size_t)nsel);
             for (long long r = 0; r < nsel; ++r) j->lin_host[(size_t)r] = (fl[r] & (SH_FLAG_PREFILTER | SH_FLAG_FILTER)) ? -1 : ml;
@@ -379,7 +519,7 @@ int sh_job_collect(sh_job *j, const char **text, int64_t *nbytes, int64_t *count
         const int64_t n = format_records_samples(s.names, s.name_off, s.counts, c->N, slot_idx(s), nsel, cols, 5, betas, s.cap_res_rows, j->q,
                                             j->q > 0 ? j->valid.data() : nullptr, lin, lin ? j->lin_ptrs.data() : nullptr, (int)j->lin_ptrs.size(),
                                             slot_flags(s), text, j->smp_order.empty() ? nullptr : s.bits, s.row_bytes, j->smp_blob.data(), j->smp_off.data(),
-                                            j->smp_order.data());
+                                            j->smp_order.data(), j->smp_order.empty() ? nullptr : s.miss);
         if (n < 0) return fail(SH_EINVAL, "sh_format_records failed");
         *nbytes = n;
     }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/seerhip.h"
+#include "common.h"
 
 #define JOB_ROWS_PER_BLOCK 1024          // 256 threads x 4 rows, row = base + i * 256 + t: coalesced flag reads, print order = (i, t) order
 
@@ -19,8 +20,11 @@
 //   1 ALL      every row                                              (--print-filtered, fixed effects: input order)
 //   2 PF       pre-filtered rows     } --print-filtered, LMM: fit_lmm returns a block's filtered tuples first (lmm.py:160-217)
 //   3 NOT_PF   the others            }
+// a record the reader skipped (sh_job_submit_calls): counted as pre-filtered, never a row of the output, whatever the pass
+#define JOB_FLAG_SKIPPED (1u << 19)
 __device__ __forceinline__ bool job_take(uint32_t f, int pred)
 {
+    if (f & JOB_FLAG_SKIPPED) return false;
     const bool pf = (f & SH_FLAG_PREFILTER) != 0, ft = (f & SH_FLAG_FILTER) != 0;
     return pred == 0 ? (!pf && !ft) : pred == 1 ? true : pred == 2 ? pf : !pf;
 }
@@ -119,6 +123,87 @@ extern "C" hipError_t shk_job_select(hipStream_t st, const uint32_t *flags, cons
     return hipMemcpyAsync(hdr, hdr_dev, 4 * sizeof(long long), hipMemcpyDeviceToHost, st);
 }
 
+// ---- call blocks (sh_job_submit_calls): rows with missing calls, filtered rows and skipped records -----------------------------------------
+// The batch behind this kernel has fitted every row from its `present` plane.  What the reference does with a variant of a VCF or an Rtab
+// before and instead of the fit is restated here per submitted row, after the batch's own fan-out (AF compaction, de-duplication):
+//   * read_variant's return for a skipped record (pyseer/input.py:345-353): loaded, pre-filtered, never a row  -> JOB_FLAG_SKIPPED;
+//   * the AF and missing-rate filters (pyseer/model.py:255-260, pyseer/lmm.py:160-167) on af = (present + missing) / N and
+//     miss = missing / N, formed as the Python expressions form them  -> af-filter, every statistic NaN;
+//   * a row with missing calls inside the filters: pre_filtering (pyseer/model.py:31-70) over the samples that have a call, then the error
+//     path -- statsmodels' MissingDataError (model.py:371-377) or the NaN that fit_lmm_block propagates (lmm.py:190-204): `prep` and a note,
+//     every other statistic NaN.
+// One wavefront per row; rows that keep the batch's results leave at once.  flags_rows (or null): the flags with SH_FLAG_PREFILTER added for
+// every row whose pattern is NOT its packed `present` row -- the rows the pattern set takes as md5 digests instead (k_job_md5_calls).
+extern "C" __global__ void __launch_bounds__(256) k_job_calls_mark(const uint8_t *__restrict__ present, const uint8_t *__restrict__ missing, int64_t row_bytes,
+                                                                    int64_t V, const int32_t *__restrict__ n_present, const int32_t *__restrict__ n_missing,
+                                                                    const int32_t *__restrict__ skip, const uint64_t *__restrict__ y1,
+                                                                    const uint64_t *__restrict__ y0, const double *__restrict__ yc, int N, int lmm,
+                                                                    int continuous, int nrow, double min_af, double max_af, double max_missing, double pret,
+                                                                    double *__restrict__ out, uint32_t *__restrict__ flags, uint32_t *__restrict__ flags_rows)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= V) return;                                                  // (the whole wavefront)
+    const int nm = n_missing[v], cnt = n_present[v] + nm;
+    const double af = (double)cnt / (double)N, miss = (double)nm / (double)N;
+    const bool skipped = skip[v] != 0;
+    const bool filtered = skipped || !(min_af <= af && af <= max_af) || miss > max_missing;
+    if (!filtered && nm == 0) {                                          // fitted from `present`: the batch's results stand
+        if (flags_rows && lane == 0) flags_rows[v] = flags[v];
+        return;
+    }
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    double prep = qnan; bool bad = false;
+    if (!filtered) {
+        const uint8_t *pr = present + v * row_bytes, *mr = missing + v * row_bytes;
+        if (!continuous) {                                              // the 2 x 2 table over the samples that have a call (y1 / y0 hold no bit at i >= N)
+            int t11 = 0, t10 = 0, t01 = 0, t00 = 0;
+            for (int b = lane; b < ((N + 7) >> 3); b += 64) {
+                const uint32_t m = mr[b], p = (uint32_t)pr[b] & ~m, a = ~(uint32_t)pr[b] & ~m & 0xFFu;
+                const uint32_t b1 = (uint32_t)(y1[b >> 3] >> (8 * (b & 7))) & 0xFFu, b0 = (uint32_t)(y0[b >> 3] >> (8 * (b & 7))) & 0xFFu;
+                t11 += __popc(p & b1); t10 += __popc(a & b1); t01 += __popc(p & b0); t00 += __popc(a & b0);
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { t11 += __shfl_xor(t11, o); t10 += __shfl_xor(t10, o); t01 += __shfl_xor(t01, o); t00 += __shfl_xor(t00, o); }
+            prep = sh_prefilter_binary(t11, t10, t01, t00, &bad);
+        } else {                                                        // Welch's t-test from the masked sums of the centred phenotype
+            double n1 = 0, s1 = 0, q1 = 0, n0 = 0, s0 = 0, q0 = 0;
+            for (int i = lane; i < N; i += 64) {
+                if ((mr[i >> 3] >> (i & 7)) & 1u) continue;
+                const double y = yc[i];
+                if ((pr[i >> 3] >> (i & 7)) & 1u) { n1 += 1.0; s1 += y; q1 += y * y; } else { n0 += 1.0; s0 += y; q0 += y * y; }
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                n1 += __shfl_xor(n1, o); s1 += __shfl_xor(s1, o); q1 += __shfl_xor(q1, o);
+                n0 += __shfl_xor(n0, o); s0 += __shfl_xor(s0, o); q0 += __shfl_xor(q0, o);
+            }
+            prep = sh_prefilter_welch(n1, s1, q1, n0, s0, q0);
+        }
+    }
+    uint32_t f;
+    if (filtered) f = SH_NOTE_AF_FILTER | SH_FLAG_PREFILTER | (skipped ? JOB_FLAG_SKIPPED : 0u);
+    else {
+        const bool failed = lmm ? prep >= pret : prep > pret;              // (lmm.py:176, model.py:266)
+        const bool pre = failed || !isfinite(prep);
+        f = (bad ? SH_NOTE_BAD_CHISQ : 0u) |
+            (pre ? (SH_NOTE_PRE_FILTER | SH_FLAG_PREFILTER) : ((lmm ? SH_NOTE_LRT_FILTER : SH_NOTE_MISSING_DATA) | SH_FLAG_FILTER));
+    }
+    for (int a = lane; a < nrow; a += 64) out[(size_t)a * (size_t)V + (size_t)v] = (a == 0 && !filtered) ? prep : qnan;
+    if (lane == 0) { flags[v] = f; if (flags_rows) flags_rows[v] = f | SH_FLAG_PREFILTER; }
+}
+
+extern "C" hipError_t shk_job_calls_mark(hipStream_t st, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t V, const int32_t *n_present,
+                                         const int32_t *n_missing, const int32_t *skip, const uint64_t *y1, const uint64_t *y0, const double *yc, int N, int lmm,
+                                         int continuous, int nrow, double min_af, double max_af, double max_missing, double pret, double *out, uint32_t *flags,
+                                         uint32_t *flags_rows)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_job_calls_mark, dim3((unsigned)((V + 3) / 4)), dim3(256), 0, st, present, missing, row_bytes, V, n_present, n_missing, skip, y1, y0, yc,
+                       N, lmm, continuous, nrow, min_af, max_af, max_missing, pret, out, flags, flags_rows);
+    return hipGetLastError();
+}
+
 // ---- --output-patterns inside the stream (round 6) ----------------------------------------------------------------------------------------
 // The reference writes, for every TESTED variant, hash_pattern(k) = base64(md5(k.view(uint8))) + "\n" with k the variant's presence vector
 // as int64 (pyseer/input.py:710-723; print loops pyseer/__main__.py:584-585, 794-795, 818-819): an md5 over 8 N bytes per variant -- 60 us
@@ -190,6 +275,57 @@ extern "C" __global__ void __launch_bounds__(256) k_job_md5(const uint64_t *__re
     for (int i = 0; i < 4; ++i) digest[(size_t)v * 4 + i] = st[i];
 }
 
+// hash_pattern of a row with missing calls (pyseer/input.py:439-454 leaves NaN in k, :710-723 hashes its bytes): the md5 of a FLOAT64 vector.
+// 0.0 is eight zero bytes, 1.0 has 0x3FF00000 as its high word, numpy's nan 0x7FF80000: here the odd words of a block carry everything and the
+// even ones are zero.  Same block structure as k_job_md5: eight samples per 64-byte block, the marker and the length in a block of their own
+// when N % 8 == 7.  One lane per row, straight from the two row-major planes (a block is one byte of each); a missing call wins over a
+// present one.  Overwrites k_job_md5's digest of the rows that are tested and hold a missing call; the other rows are left alone.
+extern "C" __global__ void __launch_bounds__(256) k_job_md5_calls(const uint8_t *__restrict__ present, const uint8_t *__restrict__ missing, int64_t row_bytes,
+                                                                   int64_t V, int N, const uint32_t *__restrict__ flags, const int32_t *__restrict__ n_missing,
+                                                                   uint32_t *__restrict__ digest)
+{
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= V || (flags[v] & SH_FLAG_PREFILTER) || n_missing[v] == 0) return;
+    const uint8_t *pr = present + v * row_bytes, *mr = missing + v * row_bytes;
+    uint32_t st[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
+    uint32_t M[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) M[i] = 0u;
+    const int nfull = N >> 3;
+    for (int b = 0; b < nfull; ++b) {
+        const uint32_t pb = pr[b], mb = mr[b];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) M[2 * i + 1] = ((mb >> i) & 1u) ? 0x7FF80000u : (((pb >> i) & 1u) ? 0x3FF00000u : 0u);
+        md5_block(st, M);
+    }
+    const int r = N & 7;
+    const uint32_t pb = r ? pr[nfull] : 0u, mb = r ? mr[nfull] : 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        M[2 * i] = i == r ? 0x80u : 0u;
+        M[2 * i + 1] = i < r ? (((mb >> i) & 1u) ? 0x7FF80000u : (((pb >> i) & 1u) ? 0x3FF00000u : 0u)) : 0u;
+    }
+    const uint64_t nbits = (uint64_t)N * 64ull;
+    if (r < 7) { M[14] = (uint32_t)nbits; M[15] = (uint32_t)(nbits >> 32); md5_block(st, M); }
+    else {
+        md5_block(st, M);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) M[i] = 0u;
+        M[14] = (uint32_t)nbits; M[15] = (uint32_t)(nbits >> 32);
+        md5_block(st, M);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) digest[(size_t)v * 4 + i] = st[i];
+}
+
+extern "C" hipError_t shk_job_md5_calls(hipStream_t st, const uint8_t *present, const uint8_t *missing, int64_t row_bytes, int64_t V, int N, const uint32_t *flags,
+                                        const int32_t *n_missing, uint32_t *digest)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_job_md5_calls, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, present, missing, row_bytes, V, N, flags, n_missing, digest);
+    return hipGetLastError();
+}
+
 // base64 of the digests of the rows that are not pre-filtered, 24 characters + "\n" each, in row order (binascii.b2a_base64): text[25 p ..]
 // for the p-th such row.  bcount: k_job_count's counts for pred = 3.
 extern "C" __global__ void __launch_bounds__(256) k_job_pat_text(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ digest, int64_t V,
@@ -235,12 +371,16 @@ extern "C" __global__ void __launch_bounds__(256) k_job_pat_text(const uint32_t 
 }
 
 // digests + text of a block's tested rows (the rows that are not pre-filtered, in row order); `text` (device, 25 V bytes) -> `h_text` (pinned)
+// missing (or null): a call block's planes -- its rows with missing calls are digested as float64 vectors (k_job_md5_calls)
 extern "C" hipError_t shk_job_patterns(hipStream_t st, const uint64_t *T, int64_t Vpad, int64_t V, int N, const uint32_t *flags, int *bcount,
-                                       long long *hdr_scratch, uint32_t *digest, char *text, char *h_text)
+                                       long long *hdr_scratch, uint32_t *digest, char *text, char *h_text, const uint8_t *present, const uint8_t *missing,
+                                       int64_t row_bytes, const int32_t *n_missing)
 {
     if (V <= 0) return hipSuccess;
     const unsigned nb = (unsigned)((V + JOB_ROWS_PER_BLOCK - 1) / JOB_ROWS_PER_BLOCK);
     hipLaunchKernelGGL(k_job_md5, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, T, Vpad, V, N, flags, digest);
+    if (missing)
+        hipLaunchKernelGGL(k_job_md5_calls, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, present, missing, row_bytes, V, N, flags, n_missing, digest);
     hipLaunchKernelGGL(k_job_count, dim3(nb), dim3(256), 0, st, flags, V, 3, 0, bcount, hdr_scratch);
     hipLaunchKernelGGL(k_job_pat_text, dim3(nb), dim3(256), 0, st, flags, digest, V, bcount, text);
     hipError_t e = hipGetLastError(); if (e != hipSuccess) return e;

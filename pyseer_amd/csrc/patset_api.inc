@@ -99,6 +99,19 @@ static int patset_insert_rows(sh_ctx *c, hipStream_t st, const uint8_t *d_bits, 
     return patset_mark(ps, st);
 }
 
+// md5 digests on the device (four words per row) of the rows that are tested and hold a missing call (job_api.inc: call blocks), on stream st
+static int patset_insert_digests(sh_ctx *c, hipStream_t st, const uint32_t *d_digest, int64_t V, const uint32_t *d_flags, const int32_t *d_n_missing)
+{
+    PatSet *ps = c->patset;
+    if (!ps) return fail(SH_EINVAL, "pattern set: sh_patset_begin has not run on this context");
+    if (V <= 0) return SH_OK;
+    std::lock_guard<std::mutex> lk(ps->mu);
+    const int rc = patset_reserve(ps, st, V); if (rc) return rc;
+    HIPCHK(shk_ps_insert_digests(st, d_digest, V, d_flags, d_n_missing, ps->k1, ps->k2, ps->slots, ps->cnt));
+    ps->ub += V;
+    return patset_mark(ps, st);
+}
+
 static int patset_stage(sh_ctx *c, const void *src, int64_t nbytes)
 {
     PatSet *ps = c->patset;

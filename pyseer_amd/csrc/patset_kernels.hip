@@ -83,6 +83,21 @@ __global__ __launch_bounds__(256) void k_ps_insert_keys(const uint64_t *__restri
     ps_count(is_new != 0, cnt);
 }
 
+// md5 digests made on the device (the job stream's call blocks: k_job_md5_calls), four words per row: the rows that are tested (no
+// SH_FLAG_PREFILTER) and hold a missing call enter as their digest, as sh_patset_add_keys takes the host's digests; one lane per row
+__global__ __launch_bounds__(256) void k_ps_insert_digests(const uint32_t *__restrict__ digest, int64_t V, const uint32_t *__restrict__ flags,
+                                                           const int32_t *__restrict__ n_missing, unsigned long long *__restrict__ k1,
+                                                           unsigned long long *__restrict__ k2, uint64_t mask, unsigned long long *__restrict__ cnt)
+{
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int is_new = 0;
+    if (v < V && !(flags[v] & SH_FLAG_PREFILTER) && n_missing[v] != 0) {
+        const uint32_t *d = digest + (size_t)v * 4;
+        is_new = ps_insert(k1, k2, mask, (uint64_t)d[0] | ((uint64_t)d[1] << 32), (uint64_t)d[2] | ((uint64_t)d[3] << 32), cnt);
+    }
+    ps_count(is_new != 0, cnt);
+}
+
 // growth: the stored pairs of the old table into the new one (the count does not move: every pair is distinct)
 __global__ __launch_bounds__(256) void k_ps_rehash(const unsigned long long *__restrict__ o1, const unsigned long long *__restrict__ o2, int64_t old_slots,
                                                    unsigned long long *__restrict__ k1, unsigned long long *__restrict__ k2, uint64_t mask,
@@ -110,6 +125,14 @@ hipError_t shk_ps_insert_keys(hipStream_t st, const uint64_t *keys, int64_t n, u
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_ps_insert_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, k1, k2, (uint64_t)(slots - 1), cnt);
+    return hipGetLastError();
+}
+
+hipError_t shk_ps_insert_digests(hipStream_t st, const uint32_t *digest, int64_t V, const uint32_t *flags, const int32_t *n_missing, unsigned long long *k1,
+                                 unsigned long long *k2, int64_t slots, unsigned long long *cnt)
+{
+    if (V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ps_insert_digests, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, digest, V, flags, n_missing, k1, k2, (uint64_t)(slots - 1), cnt);
     return hipGetLastError();
 }
 

@@ -53,6 +53,9 @@
 //   kmer_inflate=1   [0]  a reader opened by sh_reader_open_dev has the members of a BGZF file decoded by k_bgzf_inflate (inflate_kernels.hip; without
 //                    a context by the host build of the same decoder, inflate_dev.h) instead of its decoding threads, as --device-inflate asks;
 //                    on the command line it implies kmer_dev=1
+//   calls_job=1      [0]  command line: --vcf (text, BCF, --burden) and --pres through their native readers go to the job stream as parsed
+//                    (sh_job_submit_calls: rows with missing calls, filtered rows and skipped records are marked on the device), as
+//                    --device-calls asks
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -62,7 +65,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", "calls_job", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

@@ -149,7 +149,7 @@ static int64_t format_core(const char *names, const int64_t *name_off, const int
                            const double *betas, int q, const uint8_t *betas_valid, const int32_t *lineage, const char *const *lineage_labels,
                            int n_labels, const uint32_t *flags, char *out, int64_t cap, const char **own_text,
                            const uint8_t *smp_bits = nullptr, int64_t smp_row_bytes = 0, const char *smp_names = nullptr, const int64_t *smp_off = nullptr,
-                           const int32_t *smp_order = nullptr)
+                           const int32_t *smp_order = nullptr, const uint8_t *smp_bits2 = nullptr)
 {
     Inside in_;
     int nth = std::min(shost::host_cpus(), kMaxParts);
@@ -184,13 +184,14 @@ static int64_t format_core(const char *names, const int64_t *name_off, const int
                 else { *w++ = 'N'; *w++ = 'A'; }
             }
             if (smp_bits) {
-                const uint8_t *row = smp_bits + (size_t)nv * (size_t)smp_row_bytes;
+                // (smp_bits2: the missing calls of a call block -- read_variant lists a sample whose call is missing among the carriers)
+                const uint8_t *row = smp_bits + (size_t)nv * (size_t)smp_row_bytes, *row2 = smp_bits2 ? smp_bits2 + (size_t)nv * (size_t)smp_row_bytes : nullptr;
                 for (int pass = 1; pass >= 0; --pass) {                   // carriers first (kstrains), then the rest (nkstrains)
                     *w++ = '\t';
                     bool first = true;
                     for (int i = 0; i < n_samples; ++i) {
                         const int32_t sidx = smp_order[i];
-                        if ((int)((row[sidx >> 3] >> (sidx & 7)) & 1u) != pass) continue;
+                        if ((int)(((row[sidx >> 3] | (row2 ? row2[sidx >> 3] : 0)) >> (sidx & 7)) & 1u) != pass) continue;
                         if (!first) *w++ = ',';
                         const size_t k = (size_t)(smp_off[sidx + 1] - smp_off[sidx]);
                         memcpy(w, smp_names + smp_off[sidx], k); w += k; first = false;
@@ -256,10 +257,11 @@ int64_t sh_format_records(const char *names, const int64_t *name_off, const int3
 extern "C" int64_t format_records_samples(const char *names, const int64_t *name_off, const int32_t *counts, int n_samples, const int32_t *idx, int64_t nsel,
                                           const double *const *cols, int ncol, const double *betas, int64_t betas_stride, int q, const uint8_t *betas_valid,
                                           const int32_t *lineage, const char *const *lineage_labels, int n_labels, const uint32_t *flags, const char **text,
-                                          const uint8_t *smp_bits, int64_t smp_row_bytes, const char *smp_names, const int64_t *smp_off, const int32_t *smp_order)
+                                          const uint8_t *smp_bits, int64_t smp_row_bytes, const char *smp_names, const int64_t *smp_off, const int32_t *smp_order,
+                                          const uint8_t *smp_bits2)
 {
     return format_core(names, name_off, nullptr, idx, nsel, counts, n_samples, cols, ncol, betas_stride, betas, q, betas_valid, lineage, lineage_labels,
-                       n_labels, flags, nullptr, 0, text, smp_bits, smp_row_bytes, smp_names, smp_off, smp_order);
+                       n_labels, flags, nullptr, 0, text, smp_bits, smp_row_bytes, smp_names, smp_off, smp_order, smp_bits2);
 }
 
 extern "C" int sh_format_concurrency_max(int reset)

@@ -363,6 +363,24 @@ class Job(object):
             self._resync()
             _abi.check(rc)
 
+    def submit_calls(self, present, missing, n_present, n_missing, skip, names_blob, name_off, max_missing, keep=None):
+        """A block of calls (sh_job_submit_calls): present, missing (V, row_bytes) uint8 planes, n_present, n_missing, skip (V,) int32, the names
+        as for submit.  The AF window is the engine's (set_af_filter); max_missing: the largest missing rate a row may have."""
+        V, rb = present.shape
+        assert present.dtype == np.uint8 and present.flags.c_contiguous and missing.dtype == np.uint8 and missing.flags.c_contiguous and missing.shape == (V, rb)
+        for a in (n_present, n_missing, skip):
+            assert a.dtype == np.int32 and a.flags.c_contiguous and a.shape == (V,)
+        assert name_off.dtype == np.int64 and name_off.flags.c_contiguous and name_off.shape[0] == V + 1
+        nb = np.frombuffer(names_blob, dtype=np.uint8) if not isinstance(names_blob, np.ndarray) else names_blob
+        if nb.shape[0] == 0:
+            nb = np.zeros(1, dtype=np.uint8)               # (a block of nothing but skipped records has no name: the library wants a pointer)
+        self._held.append((present, missing, n_present, n_missing, skip, nb, name_off, keep))
+        rc = self._lib.sh_job_submit_calls(self._h, present.ctypes.data, missing.ctypes.data, rb, V, n_present.ctypes.data, n_missing.ctypes.data, skip.ctypes.data,
+                                           nb.ctypes.data, name_off.ctypes.data, float(max_missing))
+        if rc:
+            self._resync()
+            _abi.check(rc)
+
     def collect(self):
         """-> (memoryview of the oldest block's text, valid until this thread's next collect; (pre-filtered, tested, printed), its keep object)"""
         rc = self._lib.sh_job_collect(self._h, C.byref(self._text), C.byref(self._n), self._cnt)
@@ -372,7 +390,30 @@ class Job(object):
         held = self._held.pop(0)
         n = self._n.value
         text = (C.c_char * n).from_address(self._text.value) if n else b""
-        return memoryview(text), (self._cnt[0], self._cnt[1], self._cnt[2]), held[4]
+        return memoryview(text), (self._cnt[0], self._cnt[1], self._cnt[2]), held[-1]
+
+    def records(self):
+        """The printed rows of the block last collected as numbers (sh_job_records): (idx (nsel,) int32 -- the row's index in its block, flags
+        (nsel,) uint32, cols (nrow, nsel) float64: filter-pvalue, lrt-pvalue, beta, beta-std-err, intercept / variant_h2, the slopes).  Copies."""
+        n, st, nr = C.c_int64(), C.c_int64(), C.c_int()
+        pi, pf, pc = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _abi.check(self._lib.sh_job_records(self._h, C.byref(n), C.byref(pi), C.byref(pf), C.byref(pc), C.byref(st), C.byref(nr)))
+        n, st, nr = n.value, st.value, nr.value
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.uint32), np.zeros((nr, 0))
+        idx = np.ctypeslib.as_array(C.cast(pi, C.POINTER(C.c_int32)), (n,)).copy()
+        flags = np.ctypeslib.as_array(C.cast(pf, C.POINTER(C.c_uint32)), (n,)).copy()
+        cols = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_double)), (nr, st))[:, :n].copy()
+        return idx, flags, cols
+
+    def set_calls_timing(self, on=True):
+        _abi.check(self._lib.sh_job_set_calls_timing(self._h, int(bool(on))))
+
+    def calls_times(self):
+        """-> {kernel: (seconds, launches)} of k_job_calls_mark and k_job_md5_calls since the last call (sh_job_calls_times)"""
+        a, b, na, nb = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        _abi.check(self._lib.sh_job_calls_times(self._h, C.byref(a), C.byref(na), C.byref(b), C.byref(nb)))
+        return {"k_job_calls_mark": (a.value * 1e-3, na.value), "k_job_md5_calls": (b.value * 1e-3, nb.value)}
 
     def _resync(self):
         """After an error: pending() follows sh_job_pending (the C side's submitted - collected); blocks it no longer counts move to a list

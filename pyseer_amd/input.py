@@ -1014,11 +1014,12 @@ class CallBlock(object):
     input order and BEFORE any AF window: names (blob / off, `names` decodes them), the reader's skip reason, the packed present / missing
     rows with their counts, and per variant the text read_variant writes to stderr while it applies its records ("Multiple alleles at ...
     Skipping", "Could not parse region None"; "" for most)."""
-    __slots__ = ("blob", "off", "skip", "present", "missing", "n_present", "n_missing", "messages", "_names")
+    __slots__ = ("blob", "off", "skip", "present", "missing", "n_present", "n_missing", "messages", "_names", "msg_rows")
 
-    def __init__(self, blob, off, skip, present, missing, n_present, n_missing, messages):
+    def __init__(self, blob, off, skip, present, missing, n_present, n_missing, messages, msg_rows=None):
+        """msg_rows: the indices of the variants whose message is not empty, where the producer knows them (None: look)"""
         self.blob, self.off, self.skip, self.present, self.missing = blob, off, skip, present, missing
-        self.n_present, self.n_missing, self.messages, self._names = n_present, n_missing, messages, None
+        self.n_present, self.n_missing, self.messages, self._names, self.msg_rows = n_present, n_missing, messages, None, msg_rows
 
     def __len__(self):
         return int(self.skip.shape[0])
@@ -1043,9 +1044,10 @@ def _vcf_call_blocks(reader, engine, block_size, burden_regions=None):
         for rb in reader.raw_blocks():
             nv = rb["skip"].shape[0]
             msgs = [""] * nv
-            for i in np.nonzero(rb["skip"] == VCF_MULTI)[0]:
+            multi = np.nonzero(rb["skip"] == VCF_MULTI)[0]
+            for i in multi:
                 msgs[i] = _multi_message(reader.contig(rb["contig"][i]), int(rb["pos"][i]))
-            yield CallBlock(rb["blob"], rb["off"], rb["skip"], rb["present"], rb["missing"], rb["n_present"], rb["n_missing"], msgs)
+            yield CallBlock(rb["blob"], rb["off"], rb["skip"], rb["present"], rb["missing"], rb["n_present"], rb["n_missing"], msgs, multi)
 
     def burden():
         import ctypes as C
@@ -1118,7 +1120,8 @@ def _vcf_call_blocks(reader, engine, block_size, burden_regions=None):
             enc = [variants[v][0].encode() for v in chunk]
             off_n = np.zeros(nvar + 1, dtype=np.int64)
             np.cumsum([len(x) for x in enc], out=off_n[1:])
-            blk = CallBlock(b"".join(enc), off_n, np.zeros(nvar, dtype=np.int32), out_p, out_m, n_p, n_m, msgs)
+            blk = CallBlock(b"".join(enc), off_n, np.zeros(nvar, dtype=np.int32), out_p, out_m, n_p, n_m, msgs,
+                            np.array([i for i, m_ in enumerate(msgs) if m_], dtype=np.int64))
             blk._names = [variants[v][0] for v in chunk]
             yield blk
 
@@ -1247,7 +1250,7 @@ def _rtab_call_blocks(reader):
         bad = np.nonzero(rb["status"])[0]
         nv = int(bad[0]) if bad.size else rb["status"].shape[0]
         cb = CallBlock(rb["blob"][:rb["off"][nv]], rb["off"][:nv + 1], rb["skip"][:nv], rb["present"][:nv], rb["missing"][:nv], rb["n_present"][:nv],
-                       rb["n_missing"][:nv], [""] * nv)
+                       rb["n_missing"][:nv], [""] * nv, np.zeros(0, dtype=np.int64))
         yield cb, (ValueError(RTAB_ERRORS[int(rb["status"][nv])]) if bad.size else None)
         if bad.size:
             return
@@ -1291,6 +1294,48 @@ def iter_call_blocks_rtab_native(p, path, engine, block_size):
                 yield cb
             if error is not None:
                 raise error
+    finally:
+        reader.close()
+
+
+def say_call_block(cb):
+    """What the default route (_vcf_packed_block) writes to stderr about a CallBlock, in its order: per variant the reader's own message, then
+    "No observations of ..." for a variant nobody carries.  Only the variants that have something to say are visited."""
+    quiet = (np.asarray(cb.skip) == 0) & ((np.asarray(cb.n_present) + np.asarray(cb.n_missing)) == 0)
+    rows = cb.msg_rows if cb.msg_rows is not None else np.array([i for i, m_ in enumerate(cb.messages) if m_], dtype=np.int64)
+    rows = np.union1d(np.asarray(rows, dtype=np.int64), np.nonzero(quiet)[0])
+    if rows.shape[0]:
+        blob, off = cb.blob, cb.off
+        sys.stderr.write("".join(cb.messages[i] + ("No observations of " + bytes(blob[off[i]:off[i + 1]]).decode() + " in selected samples\n" if quiet[i] else "")
+                                 for i in rows.tolist()))
+
+
+def _job_call_block(cb):
+    """The CallBlock as Job.submit_calls takes it: C-contiguous planes and int32 counts (views of the reader's arrays where they are that already)."""
+    c = np.ascontiguousarray
+    return CallBlock(cb.blob, c(cb.off, dtype=np.int64), c(cb.skip, dtype=np.int32), c(cb.present, dtype=np.uint8), c(cb.missing, dtype=np.uint8),
+                     c(cb.n_present, dtype=np.int32), c(cb.n_missing, dtype=np.int32), cb.messages, cb.msg_rows)
+
+
+def iter_job_call_blocks_vcf(p, path, engine, block_size, burden_regions=None):
+    """The CallBlocks of a VCF / BCF (or of its burden regions) for the job stream (--device-calls: Job.submit_calls), as parsed: the stderr
+    lines of the default route are written here, block by block, and nothing else is done per variant."""
+    for cb in iter_call_blocks_vcf_native(p, path, engine, block_size, burden_regions):
+        say_call_block(cb)
+        if len(cb):
+            yield _job_call_block(cb)
+
+
+def iter_job_call_blocks_rtab(reader):
+    """The same for an Rtab through an open NativeRtabReader (closed here).  A malformed line raises read_variant's ValueError where the default
+    route raises it: behind the stderr lines of the lines before it in its block."""
+    try:
+        for cb, error in _rtab_call_blocks(reader):
+            say_call_block(cb)
+            if error is not None:
+                raise error
+            if len(cb):
+                yield _job_call_block(cb)
     finally:
         reader.close()
 
