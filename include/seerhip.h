@@ -625,6 +625,31 @@ int         sh_select_rows_dev(sh_select *s, const void *d_bits, int64_t src_row
 int         sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits,
                                 int32_t *out_counts);
 int         sh_sim_accumulate_select(sh_ctx *ctx, sh_select *sel, const uint8_t *bits, int64_t src_row_bytes, int64_t V);
+/* A call cache served the same way (k_calls_select; pyseer_amd/input.py iter_call_cache_blocks): blocks of CALLS hold a present and a missing
+ * plane of the same rows, and one pass restricts both -- the map is loaded once for the two.
+ *   calls: V host rows of each plane, src_row_bytes wide -> V host rows of each plane over the n_dst samples (pad bits zero) with n_present
+ *     and n_missing among them (int32).  Staged through the selector's pinned memory on its stream; complete at return.  A source row wider
+ *     than 32 768 bytes (262 144 samples: one wavefront's two planes in 64 KB of LDS) is refused, here and below.
+ *   calls_dev: the same for device memory (8-byte aligned); sh_select_kernel_ms: the time between stream events around its last launch.
+ *   calls_host: the rule in plain C++ on the host pool, no context and no device.
+ *   sh_job_submit_calls_select: sh_job_submit_calls for a block over the selector's n_src samples.  The source planes are uploaded once, through
+ *     the selector's pinned memory; k_calls_select writes the selected planes and their counts into the job slot's device buffer; the counts
+ *     alone come back (8 bytes a row: the printed af, and whether the LMM's per-block lineage exists), and the selected planes too when the job
+ *     lists samples (sh_job_set_samples).  The selector must belong to the job's context; its stream and the job's are ordered by events.
+ *     present, missing and skip are the caller's again at return; names and name_off until the block is collected.  Depth and refusals as
+ *     sh_job_submit_calls. */
+int         sh_select_calls(sh_select *s, const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V, uint8_t *out_present,
+                            uint8_t *out_missing, int32_t *out_n_present, int32_t *out_n_missing);
+int         sh_select_calls_dev(sh_select *s, const void *d_present, const void *d_missing, int64_t src_row_bytes, int64_t V, void *d_out_present,
+                                void *d_out_missing, int32_t *d_n_present, int32_t *d_n_missing);
+int         sh_select_kernel_ms(sh_select *s, double *ms);
+int         sh_select_calls_host(const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst,
+                                 uint8_t *out_present, uint8_t *out_missing, int32_t *out_n_present, int32_t *out_n_missing);
+int         sh_job_submit_calls_select(sh_job *job, sh_select *sel, const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V,
+                                       const int32_t *skip, const char *names, const int64_t *name_off, double max_missing);
+/* n_present and n_missing of every row of the call block last collected (those k_calls_select made, for sh_job_submit_calls_select: what the
+ * caller's "No observations of ..." lines are said from).  Valid until the next submit. */
+int         sh_job_calls_counts(sh_job *job, int64_t *V, const int32_t **n_present, const int32_t **n_missing);
 
 #ifdef __cplusplus
 }

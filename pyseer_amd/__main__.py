@@ -20,7 +20,11 @@ line by line (--python-reader; also with --gpus, and for a header that names a s
 stream as parsed (sh_job_submit_calls: the filters, the rows with missing calls and their patterns on the device, no Python per variant; same bytes out).  --wg enet (pyseer_amd/enet.py run_cli) reads k-mers and VCF, burden regions included, through the native readers
 and --pres and --python-reader line by line.  BCF 2.1 / 2.2 is read through --vcf wherever VCF text is (sniffed from the decoded bytes, whatever the file is called): natively with each
 record's GT vector reduced on the device (k_bcf_gt_pack), or by the Python reader (--python-reader, input.BcfFile).
-Not supported (out of scope): --wg rf / blup, --gpus / the packed cache with a VCF or BCF, and around BCF: .csi / .tbi indexes (burden
+--save-calls FILE writes what the native VCF / BCF / Rtab readers deliver -- names, skip reasons, messages, the present and missing planes -- as a call
+cache beside the run's usual output; --load-calls FILE reads such a cache (or one written by python -m pyseer_amd.pack over all isolates) instead of a
+text file, through the job stream: over the run's own sample list as stored, over a superset or another order of it with both planes restricted to the
+run's samples on the device on their way in (k_calls_select, sh_job_submit_calls_select); same bytes out as the text.
+Not supported (out of scope): --wg rf / blup, --gpus / the packed k-mer cache with a VCF or BCF, --wg / several devices from a call cache, and around BCF: .csi / .tbi indexes (burden
 regions stay one pass over the file), INFO and FORMAT fields other than GT, BCF1 and minor versions above 2 (refused by name), writing BCF.
 """
 import argparse
@@ -113,6 +117,9 @@ def get_options(argv=None):
                     help='Kmers file; several files are tested as one stream in the order given and read concurrently (one gzip stream inflates serially)')
     vg.add_argument('--vcf', default=None, help='VCF file. Will filter any non \'PASS\' sites')
     vg.add_argument('--pres', default=None, help='Presence/absence .Rtab matrix as produced by roary and piggy')
+    vg.add_argument('--load-calls', default=None, metavar='FILE',
+                    help='Read variants from a call cache written by --save-calls or python -m pyseer_amd.pack (--vcf / --pres) instead of parsing the '
+                         'VCF, BCF or Rtab again; the cache may hold more samples than the run, in any order (its calls are then selected on the device)')
     va.add_argument('--burden', help='VCF regions to group variants by for burden testing (requires --vcf). '
                     'The regions are assigned in one pass over the file: no index is needed or read')
     di = parser.add_argument_group('Distances')
@@ -179,6 +186,10 @@ def get_options(argv=None):
     ot.add_argument('--load-packed', default=None,
                     help='Read variants from a packed cache written by --save-packed or python -m pyseer_amd.pack instead of parsing --kmers again; the cache may '
                          'hold more samples than the run, in any order (its rows are then selected on one device)')
+    ot.add_argument('--save-calls', default=None, metavar='FILE',
+                    help='With --vcf (text or BCF, also with --burden) or --pres through the native readers: also write the parsed calls, missing ones '
+                         'included, as a call cache in stored blocks of --block_size variants (for --load-calls in later runs over the same samples, or '
+                         'any subset or order of them)')
     ot.add_argument('--cpu-eigh', action='store_true', default=False,
                     help='Decompose the similarity matrix with numpy on the host instead of rocSOLVER on the GPU')
     ot.add_argument('--no-dedup', action='store_true', default=False,
@@ -274,7 +285,16 @@ def main(argv=None):
         ctx.count_set = PatternSet(engs[0])
 
     # ---- run, report
-    prefilter, tested, printed = run(ctx, open_blocks(ctx, src, cache_stamp))
+    try:
+        prefilter, tested, printed = run(ctx, open_blocks(ctx, src, cache_stamp))
+    except BaseException:
+        if src.calls_out is not None:                      # (--save-calls: a run that fails leaves no cache)
+            src.calls_out.abort()
+        raise
+    if src.calls_out is not None:
+        src.calls_out.close()
+    if src.selector is not None:
+        src.selector.close()
     if _route.debug("cli"):
         report_cli(ctx, t_inputs, t_setup)
     if patterns is not None:

@@ -167,6 +167,14 @@ SIGNATURES = {
     "sh_select_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "sh_select_rows_host": (C.c_int, [c_u8p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, c_u8p, C.POINTER(C.c_int32)]),
     "sh_sim_accumulate_select": (C.c_int, [C.c_void_p, C.c_void_p, c_u8p, C.c_int64, C.c_int64]),
+    # a call cache served the same way (k_calls_select): both planes of a block of calls in one pass
+    "sh_select_calls": (C.c_int, [C.c_void_p, c_u8p, c_u8p, C.c_int64, C.c_int64, c_u8p, c_u8p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sh_select_calls_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sh_select_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "sh_select_calls_host": (C.c_int, [c_u8p, c_u8p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, c_u8p, c_u8p, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32)]),
+    "sh_job_calls_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "sh_job_submit_calls_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]),
 }
 
 

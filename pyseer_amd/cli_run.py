@@ -63,8 +63,38 @@ def refuse_cache_clashes(options):
         die('Several --kmers files need the native reader and cannot be combined with a packed cache\n')
 
 
+def refuse_call_cache_clashes(options):
+    """--save-calls and --load-calls against the options they do not go with (a call cache: input.py CallCacheWriter)."""
+    kmer_cache = options.save_packed or options.load_packed or options.packed_cache
+    if options.save_calls:
+        if options.load_calls:
+            die('--save-calls writes the calls a VCF, BCF or Rtab is parsed into: not available with --load-calls\n')
+        if options.kmers:
+            die('--save-calls caches VCF, BCF and Rtab calls: k-mers have --save-packed\n')
+        if options.python_reader:
+            die('--save-calls writes what the native readers deliver: not available with --python-reader\n')
+        if options.gpus is not None:
+            die('--save-calls is written by a run on one device: not available with --gpus\n')
+        if options.wg:
+            die('--save-calls is written by a per-variant run: not available with --wg\n')
+        if kmer_cache or options.packed_part:
+            die('--save-calls is no packed k-mer cache: not available with --save-packed / --load-packed / --packed-cache / --packed-part\n')
+    if options.load_calls:
+        if options.burden:
+            die('--load-calls serves the variants its cache holds: --burden regions are not applied to it (write the cache with --save-calls --burden)\n')
+        if _route.device_count(options.gpus) > 1:
+            die('--load-calls selects and tests on one device: not available with more than one device in --gpus\n')
+        if options.packed_part:
+            die('--load-calls reads one whole cache: not available with --packed-part\n')
+        if options.wg:
+            die('--load-calls serves the per-variant models: not available with --wg\n')
+        if kmer_cache:
+            die('--load-calls reads a call cache, not a packed k-mer cache: not available with --save-packed / --load-packed / --packed-cache\n')
+
+
 def validate_options(options):
     """Every refusal that needs the options alone, in the order a doubly-wrong command line is answered in."""
+    refuse_call_cache_clashes(options)
     if options.burden and not options.vcf:
         die('Burden test can only be performed with VCF input\n')
     if options.count_patterns:
@@ -140,6 +170,30 @@ def validate_loaded(options, plan, p):
             die("pyseer_amd: a packed cache over other samples than the run's own list is read on one device: not with --gpus or --packed-part\n")
     refuse_cache_clashes(options)
     return cache_selected
+
+
+def call_cache_select_mode():
+    """How --load-calls restricts a cache over other samples than the run's own list: "fused" (sh_job_submit_calls_select), "rows" (SEERHIP_ROUTE
+    calls_cache=rows: sh_select_calls, then sh_job_submit_calls) or "host" (cache_select=host: the host restatement)."""
+    if _route.route("cache_select") == "host":
+        return "host"
+    return "rows" if _route.route("calls_cache") == "rows" else "fused"
+
+
+def open_run_call_cache(path, p):
+    """--load-calls before the header line: the cache opened, once, with its own checks (a file that is no call cache or is truncated; a run sample it
+    lacks; a sample listed twice), each answered in one line, and for a cache over a superset or another order of the run's samples the one line
+    that says so.  Returns (stored names, the stored blocks' iterator of open_call_cache, the sample map -- None for the run's own list)."""
+    from .input import open_call_cache, call_cache_sample_map
+    try:
+        stored, _, _, blocks = open_call_cache(path)
+        sample_map = call_cache_sample_map(stored, [str(x) for x in p.index])
+    except (ValueError, IOError, OSError) as ex:
+        die("pyseer_amd: --load-calls: %s\n" % ex)
+    if sample_map is not None:
+        sys.stderr.write("pyseer_amd: call cache holds %d samples; the run's %d are selected on the %s\n"
+                         % (len(stored), len(p), "host" if call_cache_select_mode() == "host" else "device"))
+    return stored, blocks, sample_map
 
 
 # ---- the host set-up ---------------------------------------------------------------------------------------------------------------------------
@@ -281,7 +335,7 @@ def make_plan(options, route, stdout_fd, patterns_fd=True, cache_selected=False,
     if proc_mode is None:
         proc_mode = bool(devices and len(devices) > 1 and options.load_packed and not options.save_packed and not options.python_sink and not options.serial_sink
                          and not options.packed_part and route("job", "1") not in ("0", "py") and route("procs", "1") != "0" and stdout_fd)
-    var_type = "kmers" if options.kmers else ("vcf" if options.vcf else "Rtab")
+    var_type = "kmers" if options.kmers else ("vcf" if options.vcf else ("calls" if options.load_calls else "Rtab"))
     reader = not options.python_reader
     # --device-reader (SEERHIP_ROUTE kmer_dev=1): the sample tokens are read on the first context's device, on a stream of the reader's own
     # --device-inflate (SEERHIP_ROUTE kmer_inflate=1): that reader's BGZF members are decoded there too, on another stream of its own
@@ -298,7 +352,9 @@ def make_plan(options, route, stdout_fd, patterns_fd=True, cache_selected=False,
     # job stream as parsed -- planes with missing calls, counts, skip reasons (sh_job_submit_calls) -- instead of through _vcf_packed_block and the
     # sinks of the Python block loop.  An option: the default route of these inputs is what it was.
     native_vcf = bool(var_type == "vcf" and reader)
-    calls_job = bool((native_vcf or native_rtab) and (options.device_calls or route("calls_job", "0") == "1") and options.gpus is None)
+    # --load-calls (round 21): the stored CallBlocks of a call cache take that route by default -- as stored (a cache over the run's own samples), or
+    # with their planes restricted to the run's samples on the device on the way in (sh_job_submit_calls_select; cache_selected)
+    calls_job = bool(((native_vcf or native_rtab) and (options.device_calls or route("calls_job", "0") == "1") and options.gpus is None) or options.load_calls)
     job_path = bool((native or options.load_packed or calls_job) and not options.python_sink and not options.serial_sink and route("job", "1") != "0")
     calls_job = calls_job and job_path
     # (--lineage, round 6: fit_lineage_effect runs inside the stream, for printed rows -- sh_job_set_lineage.  The LMM's lineage is that of each
@@ -343,14 +399,24 @@ def prepare_input(options, plan, p):
     """What is opened and checked before the header line: the burden regions, the gzip check, the Python readers' file."""
     from .input import check_kmers_gzipped, load_burden, open_variant_file
     kmer_files = list(options.kmers) if options.kmers else []
-    src = SimpleNamespace(kmer_files=kmer_files, var_file=(kmer_files[0] if kmer_files else (options.vcf or options.pres)), infile=None, sample_order=None,
-                          burden_regions=(collections.deque([]) if options.burden else None), cache_out=None)
+    src = SimpleNamespace(kmer_files=kmer_files, var_file=(kmer_files[0] if kmer_files else (options.vcf or options.pres or options.load_calls)), infile=None,
+                          sample_order=None, burden_regions=(collections.deque([]) if options.burden else None), cache_out=None, calls_out=None, selector=None, call_cache=None)
+    if options.load_calls:
+        src.call_cache = open_run_call_cache(options.load_calls, p)
     if plan.native and not options.uncompressed and not options.load_packed:
         check_kmers_gzipped(kmer_files or [src.var_file])
+    if options.save_calls and plan.native_rtab:
+        # (a header that names a phenotype sample twice is read line by line, the last call that is not `0` winning: no planes to store.  The native
+        # reader's own refusal, asked for here, before the header line, by opening it without a device)
+        from .input import NativeRtabReader, RtabDuplicateSample
+        try:
+            NativeRtabReader(src.var_file, [str(x) for x in p.index], None, 1).close()
+        except RtabDuplicateSample as ex:
+            die("--save-calls needs the native Rtab reader, which does not read %s (%s)\n" % (src.var_file, ex))
     if plan.native_vcf:
         if options.burden:
             load_burden(options.burden, src.burden_regions)
-    elif not plan.native and not plan.native_rtab:
+    elif not plan.native and not plan.native_rtab and not options.load_calls:
         src.infile, src.sample_order = open_variant_file(plan.var_type, src.var_file, options.burden, src.burden_regions, options.uncompressed)
     return src
 
@@ -383,22 +449,37 @@ def open_blocks(ctx, src, cache_stamp=None, part=None, eng=None):
             src.cache_out = I.PackedCacheWriter(options.save_packed, [str(x) for x in p.index], stamp=cache_stamp)
         return I.iter_packed_blocks_native(p, src.var_file, *af, plan.job_block, want_patterns=plan.want_pat, want_samples=options.print_samples, save_to=src.cache_out,
                                            raw=plan.job_path, engine=(engs[0] if (plan.dev_reader and engs) else None), inflate=(True if options.device_inflate else None))
+    if options.load_calls:
+        # a call cache: as stored for the run's own sample list; else restricted to the run's samples -- inside the job stream (fused: the blocks go up
+        # over the stored samples, behind the selector kept in src until the run ends), or block by block before they are handed on
+        found, stored_blocks, sample_map = src.call_cache
+        mode, how = ("job" if plan.job_path else "packed"), call_cache_select_mode()
+        if sample_map is not None and how != "host":
+            from .engine import RowSelector
+            src.selector = RowSelector(engs[0], len(found), sample_map)
+            if plan.job_path and how == "fused":
+                mode = "fused"
+        return I.iter_call_cache_blocks(p, stored_blocks, plan.job_block, mode, src.selector, len(found), sample_map, options.max_missing, *af,
+                                        want_patterns=plan.want_pat)
+    if options.save_calls and (plan.native_vcf or plan.native_rtab):
+        src.calls_out = I.CallCacheWriter(options.save_calls, [str(x) for x in p.index], options.block_size)
     if plan.calls_job and plan.native_vcf:
         # (the reader and the job stream share the first context: the blocks are read on the thread that submits them, between its calls)
-        return I.iter_job_call_blocks_vcf(p, src.var_file, engs[0], plan.job_block, burden_regions=(list(src.burden_regions) if options.burden else None))
+        return I.iter_job_call_blocks_vcf(p, src.var_file, engs[0], plan.job_block, burden_regions=(list(src.burden_regions) if options.burden else None),
+                                          save_to=src.calls_out)
     if plan.calls_job:
         try:
-            return I.iter_job_call_blocks_rtab(I.NativeRtabReader(src.var_file, [str(x) for x in p.index], engs[0], plan.job_block))
+            return I.iter_job_call_blocks_rtab(I.NativeRtabReader(src.var_file, [str(x) for x in p.index], engs[0], plan.job_block), save_to=src.calls_out)
         except I.RtabDuplicateSample:
             # a header that names a sample twice is read line by line (iter_packed_blocks_rtab_native), through the Python block loop
             ctx.plan = plan = plan._replace(calls_job=False, job_path=False, job_block=options.block_size, want_pat=bool(options.output_patterns or options.count_patterns))
     if plan.native_vcf:
         # the reader uses the first context's device and stream between that context's own calls (one stream: the order is the stream's)
         return I.iter_packed_blocks_vcf_native(p, src.var_file, engs[0], *af, options.max_missing, options.block_size,
-                                               burden_regions=(list(src.burden_regions) if options.burden else None))
+                                               burden_regions=(list(src.burden_regions) if options.burden else None), save_to=src.calls_out)
     if plan.native_rtab:
         # (as above: the calls are tokenised on the first context's device; a header that names a sample twice takes the line reader by itself)
-        return I.iter_packed_blocks_rtab_native(p, src.var_file, engs[0], *af, options.max_missing, options.block_size)
+        return I.iter_packed_blocks_rtab_native(p, src.var_file, engs[0], *af, options.max_missing, options.block_size, save_to=src.calls_out)
     return I.iter_packed_blocks(p, plan.var_type, src.infile, set(p.index), src.sample_order, *af, options.max_missing, options.uncompressed,
                                 options.block_size, burden=bool(options.burden), burden_regions=src.burden_regions)
 
@@ -429,6 +510,12 @@ def run_stream_job(ctx, engs, blocks, write_text, tm, stop=None, write_patterns=
         t_c = time.perf_counter()
         text, cnt, release = jb.collect()
         tm["engine"] += time.perf_counter() - t_c
+        if getattr(release, "selector", None) is not None:
+            # a block of a call cache selected inside the stream: its counts over the run's samples exist now, and with them what say_call_block says
+            from .input import say_call_block
+            release.n_present, release.n_missing = jb.calls_counts()
+            say_call_block(release)
+            release = None
         n.prefilter += cnt[0]; n.tested += cnt[1]; n.printed += cnt[2]
         if write_patterns is not None and cnt[1]:
             write_patterns(jb.patterns())                 # (hash_pattern of the block's tested variants, made on the device)
@@ -451,7 +538,9 @@ def run_stream_job(ctx, engs, blocks, write_text, tm, stop=None, write_patterns=
             while jb.pending() >= jb.depth:
                 take()
             t_e = time.perf_counter()
-            if getattr(rb, "missing", None) is not None:  # a CallBlock of the native VCF / Rtab reader (input.iter_job_call_blocks_*)
+            if getattr(rb, "selector", None) is not None:  # a stored block of a call cache over other samples (input.iter_call_cache_blocks, "fused")
+                jb.submit_calls_select(rb.selector, rb.present, rb.missing, rb.skip, rb.blob, rb.off, ctx.options.max_missing, keep=rb)
+            elif getattr(rb, "missing", None) is not None:  # a CallBlock of the native VCF / Rtab reader (input.iter_job_call_blocks_*)
                 jb.submit_calls(rb.present, rb.missing, rb.n_present, rb.n_missing, rb.skip, rb.blob, rb.off, ctx.options.max_missing)
             else:
                 jb.submit(rb.bits, rb.counts, rb.blob, rb.off, rows_are_dma=rb.dma, keep=rb.release)

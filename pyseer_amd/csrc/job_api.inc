@@ -28,6 +28,9 @@ struct JobSlot {
     // a call block (sh_job_submit_calls): d_bits holds [present | missing | n_present, n_missing, skip] (calls_layout), miss: the caller's missing plane
     // (--print-samples), cnt_host: present + missing per row (the printed af), no_last_lineage: the block's last row was skipped or holds a missing call
     int calls = 0, no_last_lineage = 0; const uint8_t *miss = nullptr; double max_missing = 0.0; std::vector<int32_t> cnt_host;
+    // a call block selected on the device (sh_job_submit_calls_select, select_api.inc): the counts are k_calls_select's and lie in the pinned slab
+    // once ev_done has passed -- cnt_host and no_last_lineage are made from them at the collect
+    int counts_from_device = 0;
     uint32_t *d_flags_rows = nullptr; int64_t cap_frows = 0;            // --count-patterns: the flags by which the pattern set takes packed rows
     int64_t cap_dig = 0;
     int state = 0;                                                      // 0 free, 1 rows on their way, 2 kernels queued, 3 the lane that ran them failed
@@ -366,7 +369,7 @@ static int job_submit_rows(sh_job *j, const uint8_t *bits, const uint8_t *const 
     JobSlot &s = j->slot[j->n_submitted % j->depth];
     int rc = job_ensure(j, s, V, row_bytes, !rows_are_dma); if (rc) return rc;
     s.bits = bits; s.row_bytes = row_bytes; s.V = V; s.counts = counts; s.names = names; s.name_off = name_off;
-    s.calls = 0; s.miss = nullptr; s.no_last_lineage = 0;
+    s.calls = 0; s.miss = nullptr; s.no_last_lineage = 0; s.counts_from_device = 0;
     // rows -> device on the copy stream.  DMA-able where they lie (pinned or registered: the packed-cache mapping): nothing but the descriptor
     // is touched by the CPU.  Otherwise through this slot's pinned slab, filled by the caller and the idle workers of the process-wide pool.
     const uint8_t *src = bits;
@@ -428,7 +431,7 @@ int sh_job_submit_calls(sh_job *j, const uint8_t *present, const uint8_t *missin
     JobSlot &s = j->slot[j->n_submitted % j->depth];
     int rc = job_ensure(j, s, V, row_bytes, true, true); if (rc) return rc;
     s.bits = present; s.miss = missing; s.row_bytes = row_bytes; s.V = V; s.names = names; s.name_off = name_off;
-    s.calls = 1; s.max_missing = max_missing; s.no_last_lineage = (skip[V - 1] != 0 || n_missing[V - 1] != 0) ? 1 : 0;
+    s.calls = 1; s.counts_from_device = 0; s.max_missing = max_missing; s.no_last_lineage = (skip[V - 1] != 0 || n_missing[V - 1] != 0) ? 1 : 0;
     s.cnt_host.resize((size_t)V);
     for (int64_t v = 0; v < V; ++v) s.cnt_host[(size_t)v] = n_present[v] + n_missing[v];   // the printed af: (present + missing) / N (input.py:446)
     s.counts = s.cnt_host.data();
@@ -465,6 +468,19 @@ int sh_job_records(sh_job *j, int64_t *nsel, const int32_t **idx, const uint32_t
     return SH_OK;
 }
 
+// n_present and n_missing of every row of the call block last collected, as its slot's pinned slab holds them: the caller's own for
+// sh_job_submit_calls, k_calls_select's for sh_job_submit_calls_select.  Valid until the next submit.
+int sh_job_calls_counts(sh_job *j, int64_t *V, const int32_t **n_present, const int32_t **n_missing)
+{
+    if (!j || !V || !n_present || !n_missing) return fail(SH_EINVAL, "sh_job_calls_counts: null argument");
+    if (j->n_collected == 0) return fail(SH_EINVAL, "sh_job_calls_counts: nothing collected");
+    JobSlot &s = j->slot[(j->n_collected - 1) % j->depth];
+    if (!s.calls) return fail(SH_EINVAL, "sh_job_calls_counts: the block last collected was no call block");
+    const int32_t *ints = (const int32_t *)(s.hp_bits + calls_layout(s.V, s.row_bytes).ints);
+    *V = s.V; *n_present = ints; *n_missing = ints + s.V;
+    return SH_OK;
+}
+
 int64_t sh_job_pending(sh_job *j) { return j ? (int64_t)(j->n_submitted - j->n_collected) : 0; }
 int sh_job_depth(sh_job *j) { return j ? j->depth : 0; }
 
@@ -491,6 +507,12 @@ int sh_job_collect(sh_job *j, const char **text, int64_t *nbytes, int64_t *count
     const long long nsel = slot_hdr(s)[0], npf = slot_hdr(s)[1];
     if (nsel < 0 || nsel > s.V || npf < 0 || npf > s.V) return fail(SH_EHIP, "sh_job_collect: the device left an impossible count");
     counters[0] = npf; counters[1] = s.V - npf; counters[2] = nsel;
+    if (s.counts_from_device) {                                         // (the slab's counts came back on the selector's stream, which ev_done is behind)
+        const int32_t *np_ = (const int32_t *)(s.hp_bits + calls_layout(s.V, s.row_bytes).ints), *nm_ = np_ + s.V;
+        for (int64_t v = 0; v < s.V; ++v) s.cnt_host[(size_t)v] = np_[v] + nm_[v];
+        if (nm_[s.V - 1] != 0) s.no_last_lineage = 1;
+        s.counts_from_device = 0;
+    }
     *text = ""; *nbytes = 0;
     j->pat_n = 0;
     if (j->patterns) {                                                  // (the slot's pinned text may be overwritten by the block that takes the slot next)

@@ -56,6 +56,9 @@
 //   calls_job=1      [0]  command line: --vcf (text, BCF, --burden) and --pres through their native readers go to the job stream as parsed
 //                    (sh_job_submit_calls: rows with missing calls, filtered rows and skipped records are marked on the device), as
 //                    --device-calls asks
+//   calls_cache=rows [unset] command line: --load-calls of a cache over a superset or another order of the run's samples selects every block to the
+//                    host (sh_select_calls) and submits it as a reader's (sh_job_submit_calls) instead of the fused sh_job_submit_calls_select:
+//                    the A/B and the check of the fused route (cache_select=host|0 mean for this cache what they mean for the k-mer cache)
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -65,7 +68,7 @@ static inline const char *const *sh_route_keys()
 {
     static const char *const keys[] = {"chord", "chord_n32", "chord_enter", "bitdot", "first_bordered", "pk", "warm", "fin_rounds", "ll_first", "newton",
                                        "firth_last", "firth_first32", "afcompact", "complement", "reader_slab", "reader_pad", "reader_chunk", "reader_workers", "reader_depth", "reader_helpers", "reader_target",
-                                       "firth_literal", "firth_strict", "firth_fast", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", "calls_job", nullptr};
+                                       "firth_literal", "firth_strict", "firth_fast", "lmm_limbs", "lmm_tol", "qf", "ragged", "lanes", "reader", "reader_threads", "wait", "job", "dma", "procs", "dma_window", "rtab_wg", "rtab_slab", "lin_counts", "kmer_dev", "cache_select", "kmer_inflate", "calls_job", "calls_cache", nullptr};
     return keys;
 }
 // the route string in force for the calling thread: the environment's, or the one a parent context was set up under (lanes_api.inc)

@@ -10,12 +10,20 @@
 //   sh_select_rows_host   the same rule in plain C++ on the host pool, no context: the CPU tests, and the rate to compare against.
 hipError_t shk_rows_select(hipStream_t, const void *, int64_t, int64_t, const int32_t *, int, void *, int32_t *);
 int64_t shk_rows_select_max_row_bytes(void);
+//   sh_select_calls / _dev / _host   the same three for a block of CALLS (a call cache, DESIGN.md section 5.9): a present and a missing plane of the
+//                         same rows through k_calls_select, which shares one load of the map between both; the two planes of a chunk lie behind
+//                         one another in a slot's buffers, [present rows | missing rows], and so do their counts.
+//   sh_job_submit_calls_select (job_api.inc) takes the selector's staging and stream for a block on its way into a job's slot.
+hipError_t shk_calls_select(hipStream_t, const void *, const void *, int64_t, int64_t, const int32_t *, int, void *, void *, int32_t *, int32_t *);
+int64_t shk_calls_select_max_row_bytes(void);
 
 #define SELECT_CHUNK_BYTES ((int64_t)16 << 20)
 
 struct sh_select {
     sh_ctx *ctx = nullptr; int device = 0, n_src = 0, n_dst = 0;
     hipStream_t stream = nullptr;
+    uint64_t job_blocks = 0;                               // blocks sh_job_submit_calls_select has staged: block b through slot[b & 1]
+    hipEvent_t t0 = nullptr, t1 = nullptr; bool timed = false;   // around the last launch of sh_select_calls_dev (sh_select_kernel_ms)
     int32_t *d_map = nullptr;
     struct Slot { uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr; int32_t *h_counts = nullptr, *d_counts = nullptr;
                   int64_t cap_in = 0, cap_rows = 0, cap_rows_dev = 0; hipEvent_t done = nullptr, used = nullptr; } slot[2];
@@ -57,6 +65,8 @@ void sh_select_close(sh_select *s)
         if (sl.used) hipEventDestroy(sl.used);
     }
     hipFree(s->d_map);
+    if (s->t0) hipEventDestroy(s->t0);
+    if (s->t1) hipEventDestroy(s->t1);
     if (s->stream) hipStreamDestroy(s->stream);
     delete s;
 }
@@ -213,11 +223,12 @@ int sh_sim_accumulate_select(sh_ctx *c, sh_select *s, const uint8_t *bits, int64
 }
 
 // the kernel's rule in plain C++: out bit j = source bit map[j]; whole output rows are written, pad bits zero
-int sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits, int32_t *out_counts)
+static int select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits, int32_t *out_counts,
+                            const char *who)
 {
-    const int rc0 = select_check_map(n_src, map, n_dst, "sh_select_rows_host"); if (rc0) return rc0;
-    if (V < 0 || src_row_bytes <= 0 || (V > 0 && (!bits || !out_bits || !out_counts))) return fail(SH_EINVAL, "sh_select_rows_host: bad argument");
-    if (src_row_bytes * 8 < n_src) return fail(SH_ESHAPE, "sh_select_rows_host: src_row_bytes*8 < n_src");
+    const int rc0 = select_check_map(n_src, map, n_dst, who); if (rc0) return rc0;
+    if (V < 0 || src_row_bytes <= 0 || (V > 0 && (!bits || !out_bits || !out_counts))) return fail(SH_EINVAL, std::string(who) + ": bad argument");
+    if (src_row_bytes * 8 < n_src) return fail(SH_ESHAPE, std::string(who) + ": src_row_bytes*8 < n_src");
     const int64_t out_rb = (((int64_t)n_dst + 63) / 64) * 8;
     const int out_words = (n_dst + 63) >> 6;
     const std::function<void(int64_t)> fn = [&](int64_t v) {
@@ -236,5 +247,153 @@ int sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, i
     };
     shost::CpuScope cs(shost::ST_OTHER);
     shost::pool().run(V, 64, fn, shost::ST_OTHER);
+    return SH_OK;
+}
+
+int sh_select_rows_host(const uint8_t *bits, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst, uint8_t *out_bits, int32_t *out_counts)
+{
+    return select_rows_host(bits, src_row_bytes, V, n_src, map, n_dst, out_bits, out_counts, "sh_select_rows_host");
+}
+
+// ---- blocks of calls: two planes of the same rows (k_calls_select) ---------------------------------------------------------------------------
+static int select_check_calls(sh_select *s, int64_t src_row_bytes, int64_t V, const void *p, const void *m, const void *op, const void *om, const void *np,
+                              const void *nm, const char *who)
+{
+    if (!s) return fail(SH_EINVAL, std::string(who) + ": null selector");
+    int rc = select_check_rows(s->n_src, src_row_bytes, V, p, op, np, who); if (rc) return rc;
+    rc = select_check_rows(s->n_src, src_row_bytes, V, m, om, nm, who); if (rc) return rc;
+    if (src_row_bytes > shk_calls_select_max_row_bytes())
+        return fail(SH_ESHAPE, std::string(who) + ": the source row is too wide for the two planes of one wavefront of k_calls_select in LDS (at most " +
+                               std::to_string(shk_calls_select_max_row_bytes()) + " bytes)");
+    return SH_OK;
+}
+
+int sh_select_calls(sh_select *s, const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V, uint8_t *out_present, uint8_t *out_missing,
+                    int32_t *out_n_present, int32_t *out_n_missing)
+{
+    const int rc0 = select_check_calls(s, src_row_bytes, V, present, missing, out_present, out_missing, out_n_present, out_n_missing, "sh_select_calls"); if (rc0) return rc0;
+    if (V == 0) return SH_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const int64_t out_rb = (((int64_t)s->n_dst + 63) / 64) * 8;
+    const int64_t chunk = std::max<int64_t>(1, SELECT_CHUNK_BYTES / (2 * src_row_bytes)), n_chunks = (V + chunk - 1) / chunk, cap = std::min(chunk, V);
+    auto finish = [&](int64_t c) -> int {
+        sh_select::Slot &sl = s->slot[c & 1];
+        const int64_t v0 = c * chunk, nv = std::min(chunk, V - v0);
+        HIPCHK(hipEventSynchronize(sl.done));
+        select_copy(out_present + v0 * out_rb, sl.h_out, nv * out_rb);
+        select_copy(out_missing + v0 * out_rb, sl.h_out + cap * out_rb, nv * out_rb);
+        memcpy(out_n_present + v0, sl.h_counts, (size_t)nv * 4);
+        memcpy(out_n_missing + v0, sl.h_counts + cap, (size_t)nv * 4);
+        return SH_OK;
+    };
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        sh_select::Slot &sl = s->slot[c & 1];
+        if (c >= 2) { const int rc = finish(c - 2); if (rc) return rc; }
+        const int64_t v0 = c * chunk, nv = std::min(chunk, V - v0);
+        // (a slot holds `cap` rows of each plane: the missing plane, its output and its counts start `cap` rows in)
+        const int rc = select_ensure(s, sl, 2 * cap, 2 * cap * src_row_bytes, true); if (rc) return rc;
+        select_copy(sl.h_in, present + v0 * src_row_bytes, nv * src_row_bytes);
+        select_copy(sl.h_in + cap * src_row_bytes, missing + v0 * src_row_bytes, nv * src_row_bytes);
+        HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, (size_t)(nv * src_row_bytes), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipMemcpyAsync(sl.d_in + cap * src_row_bytes, sl.h_in + cap * src_row_bytes, (size_t)(nv * src_row_bytes), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(shk_calls_select(s->stream, sl.d_in, sl.d_in + cap * src_row_bytes, src_row_bytes, nv, s->d_map, s->n_dst, sl.d_out, sl.d_out + cap * out_rb,
+                                sl.d_counts, sl.d_counts + cap));
+        HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)((cap + nv) * out_rb), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_counts, sl.d_counts, (size_t)(cap + nv) * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipEventRecord(sl.done, s->stream));
+    }
+    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c) { const int rc = finish(c); if (rc) return rc; }
+    return SH_OK;
+}
+
+int sh_select_calls_dev(sh_select *s, const void *d_present, const void *d_missing, int64_t src_row_bytes, int64_t V, void *d_out_present, void *d_out_missing,
+                        int32_t *d_n_present, int32_t *d_n_missing)
+{
+    const int rc0 = select_check_calls(s, src_row_bytes, V, d_present, d_missing, d_out_present, d_out_missing, d_n_present, d_n_missing, "sh_select_calls_dev");
+    if (rc0) return rc0;
+    if ((((uintptr_t)d_present) | ((uintptr_t)d_missing) | ((uintptr_t)d_out_present) | ((uintptr_t)d_out_missing)) & 7)
+        return fail(SH_EINVAL, "sh_select_calls_dev: rows must be 8-byte aligned");
+    if (V == 0) return SH_OK;
+    HIPCHK(hipSetDevice(s->device));
+    if (!s->t0) { HIPCHK(hipEventCreate(&s->t0)); HIPCHK(hipEventCreate(&s->t1)); }
+    HIPCHK(hipEventRecord(s->t0, s->stream));
+    HIPCHK(shk_calls_select(s->stream, d_present, d_missing, src_row_bytes, V, s->d_map, s->n_dst, d_out_present, d_out_missing, d_n_present, d_n_missing));
+    HIPCHK(hipEventRecord(s->t1, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->timed = true;
+    return SH_OK;
+}
+
+// milliseconds between the stream events around the launch of the last sh_select_calls_dev (the measurement: tools/calls_cache_bench.py)
+int sh_select_kernel_ms(sh_select *s, double *ms)
+{
+    if (!s || !ms) return fail(SH_EINVAL, "sh_select_kernel_ms: null argument");
+    if (!s->timed) return fail(SH_EINVAL, "sh_select_kernel_ms: sh_select_calls_dev has not run");
+    float t = 0.0f;
+    HIPCHK(hipEventElapsedTime(&t, s->t0, s->t1));
+    *ms = (double)t;
+    return SH_OK;
+}
+
+int sh_select_calls_host(const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V, int n_src, const int32_t *map, int n_dst,
+                         uint8_t *out_present, uint8_t *out_missing, int32_t *out_n_present, int32_t *out_n_missing)
+{
+    const int rc = select_rows_host(present, src_row_bytes, V, n_src, map, n_dst, out_present, out_n_present, "sh_select_calls_host"); if (rc) return rc;
+    return select_rows_host(missing, src_row_bytes, V, n_src, map, n_dst, out_missing, out_n_missing, "sh_select_calls_host");
+}
+
+// A stored block of a call cache over n_src samples into the job stream of a run over n_dst of them (sh_job_submit_calls with the selection in
+// front).  The source planes go into the selector's pinned slot b & 1 and up, once, on the selector's stream; k_calls_select writes the selected
+// planes and their counts straight into the job slot's device buffer, in calls_layout; `skip` goes up beside them through the job slot's pinned
+// slab, and the counts -- with the planes only when the job lists samples (sh_job_set_samples reads them on the host) -- come back into that
+// slab.  The slot's ev_h2d is recorded on the selector's stream behind all of it, and the stream that runs the block's kernels waits for it,
+// as it waits for a plain block's upload.  The job slot's device buffer is free when this is called: its last block was collected, behind
+// its ev_done.  A selector slot's pinned rows are written again once the event behind their last upload and kernel has passed.
+int sh_job_submit_calls_select(sh_job *j, sh_select *sel, const uint8_t *present, const uint8_t *missing, int64_t src_row_bytes, int64_t V, const int32_t *skip,
+                               const char *names, const int64_t *name_off, double max_missing)
+{
+    if (!j) return fail(SH_EINVAL, "null job");
+    if (!sel) return fail(SH_EINVAL, "sh_job_submit_calls_select: null selector");
+    if (sel->ctx != j->c) return fail(SH_EINVAL, "sh_job_submit_calls_select: the selector belongs to another context");
+    if (!present || !missing || !skip || !names || !name_off || V <= 0) return fail(SH_EINVAL, "sh_job_submit_calls_select: bad argument");
+    int rc = select_check_calls(sel, src_row_bytes, V, present, missing, present, missing, skip, skip, "sh_job_submit_calls_select"); if (rc) return rc;
+    if (j->n_submitted - j->n_collected >= (uint64_t)j->depth) return fail(SH_EINVAL, "sh_job_submit_calls_select: every slot holds a block; collect one first");
+    sh_ctx *c = j->c;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t out_rb = (((int64_t)sel->n_dst + 63) / 64) * 8;
+    JobSlot &s = j->slot[j->n_submitted % j->depth];
+    rc = job_ensure(j, s, V, out_rb, true, true); if (rc) return rc;
+    sh_select::Slot &sl = sel->slot[sel->job_blocks & 1];
+    if (sel->job_blocks >= 2) { rc = wait_event_asleep(sl.done); if (rc) return rc; }   // (the slot's pinned rows have gone up; hipEventSynchronize spins a CPU)
+    rc = select_ensure(sel, sl, 0, 2 * V * src_row_bytes, true, false); if (rc) return rc;
+    const CallsLayout CL = calls_layout(V, out_rb);
+    const bool lists = !j->smp_order.empty();
+    s.bits = s.hp_bits; s.miss = s.hp_bits + CL.miss; s.row_bytes = out_rb; s.V = V; s.names = names; s.name_off = name_off;
+    s.calls = 1; s.counts_from_device = 1; s.max_missing = max_missing; s.no_last_lineage = skip[V - 1] != 0 ? 1 : 0;
+    s.cnt_host.assign((size_t)V, 0);
+    s.counts = s.cnt_host.data();
+    int32_t *h_ints = (int32_t *)(s.hp_bits + CL.ints);
+    select_copy(sl.h_in, present, V * src_row_bytes);
+    select_copy(sl.h_in + V * src_row_bytes, missing, V * src_row_bytes);
+    std::memcpy(h_ints + 2 * V, skip, (size_t)V * 4);
+    {
+        shost::CpuScope cs(shost::ST_SUBMIT);
+        int32_t *d_ints = (int32_t *)(s.d_bits + CL.ints);
+        HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, (size_t)(2 * V * src_row_bytes), hipMemcpyHostToDevice, sel->stream));
+        HIPCHK(hipMemcpyAsync(d_ints + 2 * V, h_ints + 2 * V, (size_t)V * 4, hipMemcpyHostToDevice, sel->stream));
+        if (CL.ints > 2 * CL.miss) { HIPCHK(hipMemsetAsync(s.d_bits + 2 * CL.miss, 0, CL.ints - 2 * CL.miss, sel->stream)); }   // (the pad: zeros, as sh_job_submit_calls uploads them)
+        HIPCHK(shk_calls_select(sel->stream, sl.d_in, sl.d_in + V * src_row_bytes, src_row_bytes, V, sel->d_map, sel->n_dst, s.d_bits, s.d_bits + CL.miss, d_ints, d_ints + V));
+        HIPCHK(hipEventRecord(sl.done, sel->stream));
+        HIPCHK(hipMemcpyAsync(h_ints, d_ints, (size_t)V * 8, hipMemcpyDeviceToHost, sel->stream));
+        if (lists) { HIPCHK(hipMemcpyAsync(s.hp_bits, s.d_bits, 2 * CL.miss, hipMemcpyDeviceToHost, sel->stream)); }
+        HIPCHK(hipEventRecord(s.ev_h2d, sel->stream));
+    }
+    ++sel->job_blocks;
+    s.state = 1;
+    ++j->n_submitted;
+    while (j->n_computed + (j->lanes > 1 ? 0 : 1) < j->n_submitted) {    // (as sh_job_submit hands the blocks' kernels over)
+        rc = job_compute(j, j->slot[j->n_computed % j->depth]); if (rc) return rc;
+        ++j->n_computed;
+    }
     return SH_OK;
 }

@@ -381,6 +381,23 @@ class Job(object):
             self._resync()
             _abi.check(rc)
 
+    def submit_calls_select(self, selector, present, missing, skip, names_blob, name_off, max_missing, keep=None):
+        """A block of calls over the selector's n_src samples (a call cache's stored block): present, missing (V, src_row_bytes) uint8, skip
+        (V,) int32, the names as for submit.  Selected on the device into the block submit_calls would take (sh_job_submit_calls_select)."""
+        V, rb = present.shape
+        assert present.dtype == np.uint8 and present.flags.c_contiguous and missing.dtype == np.uint8 and missing.flags.c_contiguous and missing.shape == (V, rb)
+        assert skip.dtype == np.int32 and skip.flags.c_contiguous and skip.shape == (V,)
+        assert name_off.dtype == np.int64 and name_off.flags.c_contiguous and name_off.shape[0] == V + 1
+        nb = np.frombuffer(names_blob, dtype=np.uint8) if not isinstance(names_blob, np.ndarray) else names_blob
+        if nb.shape[0] == 0:
+            nb = np.zeros(1, dtype=np.uint8)
+        self._held.append((present, missing, skip, nb, name_off, selector, keep))
+        rc = self._lib.sh_job_submit_calls_select(self._h, selector._h, present.ctypes.data, missing.ctypes.data, rb, V, skip.ctypes.data, nb.ctypes.data,
+                                                  name_off.ctypes.data, float(max_missing))
+        if rc:
+            self._resync()
+            _abi.check(rc)
+
     def collect(self):
         """-> (memoryview of the oldest block's text, valid until this thread's next collect; (pre-filtered, tested, printed), its keep object)"""
         rc = self._lib.sh_job_collect(self._h, C.byref(self._text), C.byref(self._n), self._cnt)
@@ -405,6 +422,12 @@ class Job(object):
         flags = np.ctypeslib.as_array(C.cast(pf, C.POINTER(C.c_uint32)), (n,)).copy()
         cols = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_double)), (nr, st))[:, :n].copy()
         return idx, flags, cols
+
+    def calls_counts(self):
+        """(n_present, n_missing) int32 copies, per row of the call block last collected (sh_job_calls_counts)."""
+        n, pp, pm = C.c_int64(), C.c_void_p(), C.c_void_p()
+        _abi.check(self._lib.sh_job_calls_counts(self._h, C.byref(n), C.byref(pp), C.byref(pm)))
+        return tuple(np.ctypeslib.as_array(C.cast(x, C.POINTER(C.c_int32)), (n.value,)).copy() for x in (pp, pm))
 
     def set_calls_timing(self, on=True):
         _abi.check(self._lib.sh_job_set_calls_timing(self._h, int(bool(on))))
@@ -526,8 +549,9 @@ def _select_rows_in(bits, n_src):
 
 class RowSelector(object):
     """Packed rows over n_src samples -> rows over the engine's samples, bit j = source bit sample_map[j] (include/seerhip.h sh_select_*,
-    k_rows_select): what serves a packed cache to a subset or another order of its samples.  sample_map: len == engine.n, distinct, each
-    in [0, n_src).  Works on a stream of its own; one thread at a time."""
+    k_rows_select): what serves a packed cache to a subset or another order of its samples; select_calls / select_calls_dev do the same for the
+    two planes of a block of calls in one pass (k_calls_select: a call cache), and Job.submit_calls_select takes the selector for a block on
+    its way into the job stream.  sample_map: len == engine.n, distinct, each in [0, n_src).  Works on a stream of its own; one thread at a time."""
 
     def __init__(self, engine, n_src, sample_map):
         self._lib = engine._lib
@@ -568,6 +592,38 @@ class RowSelector(object):
         if bits.shape[0]:
             _abi.check(self._lib.sh_sim_accumulate_select(self._eng._h, self._h, bits.ctypes.data_as(_abi.c_u8p), bits.shape[1], bits.shape[0]))
 
+    def select_calls(self, present, missing):
+        """The two planes of a block of calls, (V, src_row_bytes) uint8 host rows each -> (present', missing', n_present', n_missing') over the
+        engine's samples (sh_select_calls: k_calls_select, one pass over both planes); complete at return."""
+        present, missing = _select_rows_in(present, self.n_src), _select_rows_in(missing, self.n_src)
+        assert present.shape == missing.shape
+        V = present.shape[0]
+        out_p, out_m = np.empty((V, self.row_bytes), dtype=np.uint8), np.empty((V, self.row_bytes), dtype=np.uint8)
+        n_p, n_m = np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        _abi.check(self._lib.sh_select_calls(self._h, present.ctypes.data_as(_abi.c_u8p), missing.ctypes.data_as(_abi.c_u8p), present.shape[1], V,
+                                             out_p.ctypes.data_as(_abi.c_u8p), out_m.ctypes.data_as(_abi.c_u8p), n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32)))
+        return out_p, out_m, n_p, n_m
+
+    def select_calls_dev(self, present_t, missing_t):
+        """The same for two (V, src_row_bytes) uint8 tensors on the engine's device -> four tensors there."""
+        import torch
+        V, rb = present_t.shape
+        assert tuple(missing_t.shape) == (V, rb)
+        dev = present_t.device
+        out_p, out_m = (torch.empty((V, self.row_bytes), dtype=torch.uint8, device=dev) for _ in range(2))
+        n_p, n_m = (torch.empty((V,), dtype=torch.int32, device=dev) for _ in range(2))
+        torch.cuda.current_stream(dev).synchronize()                  # (the selector's stream is its own: the rows must be there)
+        _abi.check(self._lib.sh_select_calls_dev(self._h, C.c_void_p(present_t.data_ptr()), C.c_void_p(missing_t.data_ptr()), rb, V, C.c_void_p(out_p.data_ptr()),
+                                                 C.c_void_p(out_m.data_ptr()), C.c_void_p(n_p.data_ptr()), C.c_void_p(n_m.data_ptr())))
+        return out_p, out_m, n_p, n_m
+
+    def kernel_seconds(self):
+        """The time between the stream events around the launch of the last select_calls_dev (sh_select_kernel_ms)."""
+        ms = C.c_double()
+        _abi.check(self._lib.sh_select_kernel_ms(self._h, C.byref(ms)))
+        return ms.value * 1e-3
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.sh_select_close(self._h)
@@ -591,4 +647,19 @@ def select_rows_host(bits, n_src, sample_map):
     return out, counts
 
 
-__all__ = ["Engine", "Job", "PatternSet", "RowSelector", "hash_rows", "select_rows_host", "pack_variants", "row_bytes_for"]
+def select_calls_host(present, missing, n_src, sample_map):
+    """RowSelector.select_calls by the host restatement (sh_select_calls_host; no device): -> (present', missing', n_present', n_missing')."""
+    n_src, m, mp = _select_map(n_src, sample_map)
+    present, missing = _select_rows_in(present, n_src), _select_rows_in(missing, n_src)
+    assert present.shape == missing.shape
+    V = present.shape[0]
+    rb = row_bytes_for(m.shape[0])
+    out_p, out_m = np.empty((V, rb), dtype=np.uint8), np.empty((V, rb), dtype=np.uint8)
+    n_p, n_m = np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    _abi.check(_abi.load().sh_select_calls_host(present.ctypes.data_as(_abi.c_u8p), missing.ctypes.data_as(_abi.c_u8p), present.shape[1], V, n_src, mp, int(m.shape[0]),
+                                                out_p.ctypes.data_as(_abi.c_u8p), out_m.ctypes.data_as(_abi.c_u8p), n_p.ctypes.data_as(i32), n_m.ctypes.data_as(i32)))
+    return out_p, out_m, n_p, n_m
+
+
+__all__ = ["Engine", "Job", "PatternSet", "RowSelector", "hash_rows", "select_rows_host", "select_calls_host", "pack_variants", "row_bytes_for"]

@@ -7,6 +7,8 @@ into packed bit rows.  VCF input (pyseer/input.py:250-266, 383-407, 455-503) is 
 (the `--python-reader` path and the yardstick) or by the native reader whose sample columns are tokenised on the device (`NativeVcfReader`,
 csrc/vcf_reader.cpp + csrc/vcf_kernels.hip).  BCF 2.1 / 2.2, sniffed from the decoded bytes, takes the same two routes: `BcfFile`, and the
 native reader, which sends each record's GT vector to k_bcf_gt_pack.  No tabix index is read: burden regions are assigned in one pass over the file.
+The CallBlocks of the native VCF / BCF / Rtab readers can be kept in a call cache (`CallCacheWriter`, `open_call_cache`, `iter_call_cache_blocks`:
+--save-calls / --load-calls) and served to any subset or order of its samples, as the packed cache serves k-mer rows.
 """
 import binascii
 import gzip
@@ -1128,15 +1130,17 @@ def _vcf_call_blocks(reader, engine, block_size, burden_regions=None):
     return burden() if burden_regions is not None else plain()
 
 
-def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, burden_regions=None):
+def iter_packed_blocks_vcf_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, burden_regions=None, save_to=None):
     """The PackedBlock stream of iter_packed_blocks(p, 'vcf', ...) fed by the native reader (_vcf_call_blocks; burden_regions: one variant per
-    entry of the (name, [region, ...]) list load_burden fills)."""
+    entry of the (name, [region, ...]) list load_burden fills).  save_to: a CallCacheWriter that takes every CallBlock as read (--save-calls)."""
     samples = [str(x) for x in p.index]
     order = sorted(range(len(samples)), key=lambda i: samples[i])
     n = len(samples)
     reader = NativeVcfReader(path, samples, engine, block_size)
     try:
         for cb in _vcf_call_blocks(reader, engine, block_size, burden_regions):
+            if save_to is not None:
+                save_to.write(cb)
             yield _vcf_packed_block(n, samples, order, cb.names, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing,
                                     min_af, max_af, max_missing, want_patterns, cb.messages)
     finally:
@@ -1256,7 +1260,7 @@ def _rtab_call_blocks(reader):
             return
 
 
-def iter_packed_blocks_rtab_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True):
+def iter_packed_blocks_rtab_native(p, path, engine, min_af, max_af, max_missing, block_size, want_patterns=True, save_to=None):
     """The PackedBlock stream of iter_packed_blocks(p, 'Rtab', ...) fed by the native reader: same names, af (present + missing over n), sample
     lists, statuses, dense k for rows with missing calls, patterns and stderr lines.  A malformed line raises read_variant's ValueError once
     every complete block before it has been yielded and the lines before it in its own block have said what read_variant says of them -- the
@@ -1273,6 +1277,8 @@ def iter_packed_blocks_rtab_native(p, path, engine, min_af, max_af, max_missing,
         return
     try:
         for cb, error in _rtab_call_blocks(reader):
+            if save_to is not None:                    # (--save-calls; a malformed line ends the run, and the run's end without close() leaves no cache)
+                save_to.write(cb)
             blk = _vcf_packed_block(n, samples, order, cb.names, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing,
                                     min_af, max_af, max_missing, want_patterns)
             if error is not None:
@@ -1317,20 +1323,24 @@ def _job_call_block(cb):
                      c(cb.n_present, dtype=np.int32), c(cb.n_missing, dtype=np.int32), cb.messages, cb.msg_rows)
 
 
-def iter_job_call_blocks_vcf(p, path, engine, block_size, burden_regions=None):
+def iter_job_call_blocks_vcf(p, path, engine, block_size, burden_regions=None, save_to=None):
     """The CallBlocks of a VCF / BCF (or of its burden regions) for the job stream (--device-calls: Job.submit_calls), as parsed: the stderr
     lines of the default route are written here, block by block, and nothing else is done per variant."""
     for cb in iter_call_blocks_vcf_native(p, path, engine, block_size, burden_regions):
+        if save_to is not None:
+            save_to.write(cb)
         say_call_block(cb)
         if len(cb):
             yield _job_call_block(cb)
 
 
-def iter_job_call_blocks_rtab(reader):
+def iter_job_call_blocks_rtab(reader, save_to=None):
     """The same for an Rtab through an open NativeRtabReader (closed here).  A malformed line raises read_variant's ValueError where the default
     route raises it: behind the stderr lines of the lines before it in its block."""
     try:
         for cb, error in _rtab_call_blocks(reader):
+            if save_to is not None:
+                save_to.write(cb)
             say_call_block(cb)
             if error is not None:
                 raise error
@@ -1628,6 +1638,250 @@ def packed_cache_complete(path):
         return False
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Call cache: the CallBlocks of a VCF / BCF (single records or burden regions) or an Rtab, so that further runs over the same samples, a subset
+# or another order of them skip the text.  What does not depend on the run's samples is stored as read (names, skip, the readers' messages);
+# the planes are stored over the cache's sample list and restricted to the run's when they are loaded (k_calls_select), where the two counts
+# and the "No observations of ..." lines are made anew (say_call_block).
+#   header: b"SEERCL01", uint32 n_samples, uint32 row_bytes, uint64 len, sample names joined by "\n", zeros up to a multiple of 8
+#   blocks: uint64 nv, uint64 name_bytes, uint64 msg_bytes, uint64 0, int64 name_off[nv+1], int64 msg_off[nv+1], int32 skip[nv], int32 n_present[nv],
+#           int32 n_missing[nv], names, messages, zeros up to a multiple of 8, uint8 present[nv*row_bytes], uint8 missing[nv*row_bytes]; nv = 0 ends
+# Every block starts, and its planes start, on a multiple of 8 (row_bytes is one): a mapped plane can be read as 64-bit words.
+# ---------------------------------------------------------------------------------------------------------------
+_CL_MAGIC = b"SEERCL01"
+
+
+def _pad8(n):
+    return (-n) % 8
+
+
+class CallCacheWriter(object):
+    """CallBlocks in, re-cut into stored blocks of `block_rows` variants (a loader never splits a stored block: block_rows is the --block_size
+    of the runs the cache is for).  Written to `path + ".part"`, ended by a terminator, fsynced and renamed in close(), as PackedCacheWriter:
+    a run that fails or is interrupted (abort(), or no close() at all) leaves no cache."""
+
+    def __init__(self, path, samples, block_rows=3000):
+        self._path, self._tmp, self._rows, self._held, self._n_held = path, path + ".part", int(block_rows), [], 0
+        self.n_samples, self.row_bytes = len(samples), row_bytes_for(len(samples))
+        self._f = open(self._tmp, "wb")
+        names = "\n".join(samples).encode()
+        head = _CL_MAGIC + np.array([self.n_samples, self.row_bytes], dtype="<u4").tobytes() + np.array([len(names)], dtype="<u8").tobytes() + names
+        self._f.write(head + b"\0" * _pad8(len(head)))
+
+    def write(self, cb):
+        """One CallBlock over the cache's samples, any number of variants."""
+        if len(cb) == 0:
+            return
+        if cb.present.shape[1] != self.row_bytes or cb.missing.shape != cb.present.shape:
+            raise ValueError("call cache: planes of %d bytes a row, %d expected" % (cb.present.shape[1], self.row_bytes))
+        names = [bytes(cb.blob[cb.off[i]:cb.off[i + 1]]) for i in range(len(cb))]
+        self._held.append((names, [m_.encode() for m_ in cb.messages], np.asarray(cb.skip), np.asarray(cb.present), np.asarray(cb.missing),
+                           np.asarray(cb.n_present), np.asarray(cb.n_missing)))
+        self._n_held += len(cb)
+        while self._n_held >= self._rows:
+            self._store(self._rows)
+
+    def _store(self, nv):
+        """The first nv held variants as one stored block."""
+        parts, left, rest = [], nv, []
+        for item in self._held:
+            n = len(item[0])
+            if left >= n:
+                parts.append(item); left -= n
+            elif left > 0:
+                parts.append(tuple(x[:left] for x in item)); rest.append(tuple(x[left:] for x in item)); left = 0
+            else:
+                rest.append(item)
+        self._held, self._n_held = rest, self._n_held - nv
+        names = [x for it in parts for x in it[0]]
+        msgs = [x for it in parts for x in it[1]]
+        name_off, msg_off = np.zeros(nv + 1, dtype="<i8"), np.zeros(nv + 1, dtype="<i8")
+        np.cumsum([len(x) for x in names], out=name_off[1:])
+        np.cumsum([len(x) for x in msgs], out=msg_off[1:])
+        f = self._f
+        f.write(np.array([nv, int(name_off[-1]), int(msg_off[-1]), 0], dtype="<u8").tobytes())
+        f.write(name_off.tobytes() + msg_off.tobytes())
+        for k in (2, 5, 6):
+            f.write(np.ascontiguousarray(np.concatenate([it[k] for it in parts]), dtype="<i4").tobytes())
+        f.write(b"".join(names) + b"".join(msgs))
+        f.write(b"\0" * _pad8(12 * nv + int(name_off[-1]) + int(msg_off[-1])))
+        for k in (3, 4):
+            for it in parts:
+                f.write(np.ascontiguousarray(it[k], dtype=np.uint8).tobytes())
+
+    def close(self):
+        if self._f is not None:
+            try:
+                if self._n_held:
+                    self._store(self._n_held)
+                self._f.write(b"\0" * 32)
+                self._f.flush()
+                os.fsync(self._f.fileno())
+            except BaseException:
+                self.abort()
+                raise
+            self._f.close()
+            self._f = None
+            os.replace(self._tmp, self._path)
+
+    def abort(self):
+        """Drop what was written (the run did not finish): no cache."""
+        if self._f is not None:
+            try:
+                self._f.close()
+            except (IOError, OSError):
+                pass
+            self._f = None
+            try:
+                os.remove(self._tmp)
+            except OSError:
+                pass
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:
+            pass
+
+
+def open_call_cache(path):
+    """A call cache mapped -> (stored sample names, stored row width, rows in all, blocks): blocks() yields every stored block as a CallBlock
+    over the STORED samples whose planes are views of the mapping.  Every block header is walked here, before a plane is read: a file that is
+    no call cache, or is truncated, raises IOError now."""
+    import mmap
+    cut = IOError("truncated call cache %s (delete it, or run without --load-calls)" % path)
+    with open(path, "rb") as f:
+        size = os.fstat(f.fileno()).st_size
+        magic = f.read(8)
+        if magic == _PK_MAGIC:
+            raise IOError("%s is a packed k-mer cache, not a call cache (it is read by --load-packed)" % path)
+        if magic != _CL_MAGIC:
+            raise IOError("%s is not a call cache" % path)
+        if size < 24:
+            raise cut
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    ns, rb = (int(x) for x in np.frombuffer(mm, dtype="<u4", count=2, offset=8))
+    ln = int(np.frombuffer(mm, dtype="<u8", count=1, offset=16)[0])
+    pos = 24 + ln + _pad8(24 + ln)
+    if pos > size:
+        raise cut
+    stored = mm[24:24 + ln].decode().split("\n")
+    if len(stored) != ns or rb != row_bytes_for(ns):
+        raise IOError("call cache %s: its header does not agree with its sample list" % path)
+    index = []
+    while True:
+        if pos + 32 > size:
+            raise cut
+        nv, nb, mb, _ = (int(x) for x in np.frombuffer(mm, dtype="<u8", count=4, offset=pos))
+        if nv == 0:
+            break
+        meta = 16 * (nv + 1) + 12 * nv + nb + mb
+        end = pos + 32 + meta + _pad8(meta) + 2 * nv * rb
+        if end > size:
+            raise cut
+        index.append((pos + 32, nv, nb, mb))
+        pos = end
+
+    def blocks():
+        for at, nv, nb, mb in index:
+            name_off = np.frombuffer(mm, dtype="<i8", count=nv + 1, offset=at)
+            msg_off = np.frombuffer(mm, dtype="<i8", count=nv + 1, offset=at + 8 * (nv + 1))
+            ints = np.frombuffer(mm, dtype="<i4", count=3 * nv, offset=at + 16 * (nv + 1)).reshape(3, nv)
+            text = at + 16 * (nv + 1) + 12 * nv
+            blob = mm[text:text + nb]
+            msgs = mm[text + nb:text + nb + mb]
+            said = np.nonzero(np.diff(msg_off))[0]
+            messages = [""] * nv
+            for i in said:
+                messages[i] = msgs[msg_off[i]:msg_off[i + 1]].decode()
+            planes = text + nb + mb + _pad8(12 * nv + nb + mb)
+            present = np.frombuffer(mm, dtype=np.uint8, count=nv * rb, offset=planes).reshape(nv, rb)
+            missing = np.frombuffer(mm, dtype=np.uint8, count=nv * rb, offset=planes + nv * rb).reshape(nv, rb)
+            yield CallBlock(blob, name_off, ints[0], present, missing, ints[1], ints[2], messages, said.astype(np.int64))
+    return stored, rb, sum(x[1] for x in index), blocks
+
+
+def join_call_blocks(group):
+    """Whole CallBlocks behind one another as one."""
+    if len(group) == 1:
+        return group[0]
+    blob = b"".join(bytes(g.blob) for g in group)
+    base = np.cumsum([0] + [len(g.blob) for g in group[:-1]])
+    rows = np.cumsum([0] + [len(g) for g in group[:-1]])
+    off = np.concatenate([np.asarray(g.off[:-1]) + b for g, b in zip(group, base)] + [np.array([len(blob)], dtype=np.int64)])
+    cat = lambda k: np.concatenate([getattr(g, k) for g in group])
+    return CallBlock(blob, off, cat("skip"), cat("present"), cat("missing"), cat("n_present"), cat("n_missing"), [m_ for g in group for m_ in g.messages],
+                     np.concatenate([np.asarray(g.msg_rows, dtype=np.int64) + r for g, r in zip(group, rows)]))
+
+
+def call_cache_sample_map(stored, samples):
+    """None where the cache's sample list is the run's own; else map[j] = the position of run sample j among the stored names.  ValueError, in
+    one line, for a run sample the cache lacks, a sample listed twice on either side, or -- SEERHIP_ROUTE cache_select=0 -- any other list."""
+    if stored == samples:
+        return None
+    if _route.route("cache_select") == "0":
+        raise ValueError("call cache was written for a different sample list / order (%d vs %d samples)" % (len(stored), len(samples)))
+    where = {}
+    for i, s in enumerate(stored):
+        if s in where:
+            raise ValueError("the call cache lists sample %s twice: it is served to its own sample list only" % s)
+        where[s] = i
+    seen = set()
+    for s in samples:
+        if s not in where:
+            raise ValueError("the call cache does not hold sample %s of the run" % s)
+        if s in seen:
+            raise ValueError("sample %s is listed twice in the run: a call cache is selected for distinct samples" % s)
+        seen.add(s)
+    return np.array([where[s] for s in samples], dtype=np.int32)
+
+
+class SelectCallBlock(CallBlock):
+    """A stored block over the cache's samples on its way to Job.submit_calls_select: n_present / n_missing are those of the stored samples until the
+    device has selected it; the consumer says what say_call_block says once the block's own counts are back (Job.calls_counts)."""
+    __slots__ = ("selector",)
+
+
+def iter_call_cache_blocks(p, blocks, job_block, mode, selector=None, n_src=0, sample_map=None, max_missing=0.05, min_af=0.01, max_af=0.99, want_patterns=True):
+    """The stream of a run from a call cache; blocks: the stored blocks' iterator open_call_cache returns.  Stored blocks are joined, whole, into groups
+    of at most job_block variants (a stored block that is larger goes alone).
+    mode "job": CallBlocks for Job.submit_calls, restricted to the run's samples where sample_map is given -- by selector.select_calls, or with
+    selector None by the host restatement -- with their stderr lines said here; "fused": SelectCallBlocks over the stored samples for
+    Job.submit_calls_select; "packed": the PackedBlocks of the Python block loop (_vcf_packed_block, which says the lines itself; want_patterns as there)."""
+    from . import engine as _engine
+    samples = [str(x) for x in p.index]
+    order = sorted(range(len(samples)), key=lambda i: samples[i])
+
+    def groups():
+        acc, rows = [], 0
+        for cb in blocks():
+            if acc and rows + len(cb) > job_block:
+                yield join_call_blocks(acc)
+                acc, rows = [], 0
+            acc.append(cb); rows += len(cb)
+        if acc:
+            yield join_call_blocks(acc)
+    for cb in groups():
+        if mode == "fused":
+            cb = _job_call_block(cb)
+            out = SelectCallBlock(cb.blob, cb.off, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing, cb.messages, cb.msg_rows)
+            out.selector = selector
+            yield out
+            continue
+        if sample_map is not None:
+            if selector is not None:
+                sel = selector.select_calls(cb.present, cb.missing)
+            else:
+                sel = _engine.select_calls_host(cb.present, cb.missing, n_src, sample_map)
+            cb = CallBlock(cb.blob, cb.off, cb.skip, sel[0], sel[1], sel[2], sel[3], cb.messages, cb.msg_rows)
+        if mode == "packed":
+            yield _vcf_packed_block(len(samples), samples, order, cb.names, cb.skip, cb.present, cb.missing, cb.n_present, cb.n_missing, min_af, max_af,
+                                    max_missing, want_patterns, cb.messages)
+        else:
+            say_call_block(cb)
+            yield _job_call_block(cb)
+
+
 class _DmaWindows(object):
     """Windows of the packed-cache mapping registered with the HIP runtime (sh_host_register) so that a block's rows go from the page cache
     to the device by DMA, with no CPU copy (4 ns of CPU per 632-byte row against 21 for the copy into pinned staging:
@@ -1796,6 +2050,8 @@ def check_packed_cache(p, path, select=None):
     samples = [str(x) for x in p.index]
     with open(path, "rb") as f:
         head = f.read(24)
+        if head[:8] == _CL_MAGIC:
+            raise IOError("%s is a call cache, not a packed k-mer cache (it is read by --load-calls)" % path)
         if len(head) < 24 or head[:8] != _PK_MAGIC:
             raise IOError("%s is not a packed k-mer cache" % path)
         ns, rb = np.frombuffer(head, dtype="<u4", count=2, offset=8)
@@ -1824,6 +2080,8 @@ def _map_packed_cache(path):
         mm.madvise(mmap.MADV_SEQUENTIAL)
     except (AttributeError, OSError):
         pass
+    if mm[:8] == _CL_MAGIC:
+        raise IOError("%s is a call cache, not a packed k-mer cache (it is read by --load-calls)" % path)
     if mm[:8] != _PK_MAGIC:
         raise IOError("%s is not a packed k-mer cache" % path)
     ns, rb = np.frombuffer(mm, dtype="<u4", count=2, offset=8)
